@@ -12,8 +12,14 @@ whole hot path: arrival-stream generation, RedQueen sweep, metric scan
 (time_in_top_k K=1, average_rank, int_r_2, num_events, world_events), then for
 N>1 the RCCL all-gather of the per-replica metric rows and the ensemble means.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR also writes what the last timed step returned (DIR/<name>.npy).
+--full adds the measurements that take runs of their own after the timed region: the
+serialised per-kernel probe and the roofline built on it, the stamped PMC traffic, and
+the CPU baselines.
 """
 import argparse
 import json
@@ -45,6 +51,7 @@ MERGE_B_PER_WALL_EVENT = 18     # rq_merge_streams: read the arrival (8), write 
 SWEEP_B_PER_ROW = 24            # write t f64 + sumR f64 + nvalid u32 + cnt[K=1] u32
 SCAN_B_PER_ROW = 24             # read the same row back
 GEN_B_PER_WALL_EVENT = 8        # write one arrival time
+DUMP_MAX_ROWS = 500_000         # --dump-outputs: 8 float64 columns per replica, 32 MB
 
 
 def e2e_gbs(events_per_s):
@@ -224,6 +231,103 @@ def make_step(wl, g, so, R, world, rank, dev, Ks, group=None, force=False, chunk
     return step, R * world, dict(q=so["q"], s=so["s"], n_rep=R, randomize=True, Ks=Ks, chunk=chunk)
 
 
+def dump_outputs(path, res, means):
+    """What the last timed step returned, as path/<name>.npy (float64): the per-replica
+    metric rows [R, len(Ks) + 2], counts [R, 4] and status [R] of this rank's BatchResult,
+    and the ensemble means.  Counts and status are integers far below 2**53, so float64
+    holds them exactly.  The defaults write 0.6 MB (C3) to 16 MB (C4); past
+    DUMP_MAX_ROWS replicas (32 MB) a fixed seeded sample of the rows is written, with
+    its row numbers as rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    out = {"means": means}
+    if res is not None:   # a rank without replicas has no BatchResult
+        out.update(metrics=res.metrics, counts=res.counts, status=res.status)
+        n = res.status.shape[0]
+        if n > DUMP_MAX_ROWS:
+            rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ROWS, replace=False))
+            idx = torch.as_tensor(rows, device=res.status.device)
+            out = {k: (v if k == "means" else v[idx]) for k, v in out.items()}
+            out["rows"] = idx
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"),
+                np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float64)))
+
+
+def full_fields(a, L, g, so, pkw, plan, R, Ks, rank, world, sweep_ms, ev_rank, rows_step,
+                posts_step):
+    """--full: the result line's fields that take runs of their own after the timed region:
+    the serialised probe and the sweep's roofline over it, the stamped PMC traffic, and
+    the CPU baselines."""
+    # the kernels alone (outside the timed region): the roofline's launch duration
+    sms, snl = serial_probe(L, g, pkw, plan["chunk"],
+                            a.probe_steps or (1 if a.workload == "c5" else 3))
+
+    # roofline of the dominant kernel (the sweep), per launch, this rank
+    sweep_ms_serial = float(sms[1]) if snl[1] else None
+    # the fused sweep (variant >= 10) generates its arrivals in LDS: no arrival reads
+    fused = 10 <= plan["variant"] < 20   # 20+: the fused sweep on merged streams (reads them)
+    merged = not fused and plan["sources_per_lane"] == 0   # rq_merge_streams feeds the sweep
+    b_wall = MRG_SWEEP_B_PER_WALL_EVENT if merged else SWEEP_B_PER_WALL_EVENT
+    sweep_bytes = (0 if fused else b_wall * (ev_rank - posts_step)) + \
+        SWEEP_B_PER_ROW * rows_step
+    achieved_live = sweep_bytes / (sweep_ms * 1e-3) / 1e9
+    # the headline fraction: the kernel's own launch duration (serialised probe); the
+    # overlapped HIP-event time of the timed region is kept as frac_live
+    achieved = sweep_bytes / (sweep_ms_serial * 1e-3) / 1e9 if sweep_ms_serial else achieved_live
+
+    traffic, traffic_src, issue = pmc_traffic(a.workload, R, plan)
+    if issue and "issue_frac" in issue:
+        # the same ceiling over this run's own HIP-event launch time at the PMC run's clock
+        issue["issue_frac_2400mhz_probe_time"] = issue["valu_insts"] / (
+            N_CU * 4 * 2.4e9 / 2.0 * (sweep_ms_serial or sweep_ms) * 1e-3)
+
+    cpu = None
+    if rank == 0 and world == 1 and not a.no_cpu:
+        nt = min(16, os.cpu_count() or 1)
+        sample = a.cpu_sample or {"c5": 2, "c4": 512}.get(a.workload, 128) * nt
+        cgrid = None
+        if a.workload == "c4":   # 16 grid points spread over the q x s grid
+            from redqueen_amd import graphs
+            cgrid = graphs.c4_grid()[::16]
+        crate, cev, cel = cpu_baseline(so, nt, sample, Ks, cgrid)
+        cpu = {"value": crate, "unit": "replicas/s", "cores": nt, "kind": "port",
+               "sample": "%d %s replicas through the C oracle (engine semantics + Appendix-B "
+                         "metrics), %d pthreads, %.1f s, %.0f events/s" %
+                         (sample, a.workload.upper(), nt, cel, cev)}
+
+    return {
+        # the timed region's launches alone on the chip (serial_probe: pipeline off, one stream)
+        "kernels_ms_per_launch_serial": {"gen_streams": float(sms[0]), "merge_streams": float(sms[4]),
+                                         "sweep": sweep_ms_serial, "scan": float(sms[2]),
+                                         "launches": [int(x) for x in snl]},
+        "roofline": {"bound": "hbm", "kernel": "rq_sweep", "achieved": achieved,
+                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                     "duration_ms": sweep_ms_serial or sweep_ms,
+                     "duration_source": "serial_probe: the launch alone on the chip, HIP events"
+                                        if sweep_ms_serial else "timed region, HIP events",
+                     "bytes_per_launch": sweep_bytes,
+                     "achieved_live": achieved_live, "frac_live": achieved_live / HBM_PEAK_GBS,
+                     "traffic": traffic,
+                     "traffic_source": traffic_src,
+                     # what does bound it: SQ issue / wait shares of the wave cycles and
+                     # issue_frac = VALU instructions / the VALU issue ceiling (same PMC run)
+                     "issue": issue,
+                     "issue_frac": issue.get("issue_frac") if issue else None,
+                     "wave_slot_occupancy": issue.get("wave_slot_occupancy") if issue else None,
+                     # the same algorithmic bytes over the launch's duration with every
+                     # kernel serialised (stamped PMC summary, AMD_SERIALIZE_KERNEL=3
+                     # trace): in the timed run the two streams' kernels share the chip,
+                     # which stretches each launch's HIP-event time
+                     "frac_serialized": (sweep_bytes / (issue["serial_avg_ms"] * 1e-3) / 1e9 /
+                                         HBM_PEAK_GBS) if issue and issue.get("serial_avg_ms") else None,
+                     "note": "sweep is latency/issue-bound (serial event chain per replica); "
+                             "algorithmic bytes = 24 B/pivot row written%s" %
+                             ("" if fused else " + %d B/wall event read" % b_wall)},
+        "cpu_baseline": cpu,
+        "cpu_baseline_reference": ref_cpu_baseline(a.workload),
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -255,7 +359,18 @@ def main():
     ap.add_argument("--dist", action="store_true",
                     help="at N = 1 too: a world-size-1 RCCL group, the step's all-gather "
                          "runs through it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned on "
+                         "rank 0 (per-replica metrics, counts and status, and the ensemble "
+                         "means) as DIR/<name>.npy in float64; the seeds depend only on the "
+                         "arguments, so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the serialised per-kernel probe "
+                         "(roofline of the sweep, stamped PMC traffic) and the CPU baselines, "
+                         "and report them in the result line")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -324,11 +439,12 @@ def main():
         for st in streams:
             with torch.cuda.stream(st):
                 accs.append(new_acc())
+        res = means = None
         for k in ks:
             with torch.cuda.stream(streams[k % len(streams)]):
                 res, means = step(k)
                 accumulate(res, accs[k % len(streams)])
-        return accs
+        return accs, (res, means)   # the last step's outputs, as its caller receives them
 
     # the warmup runs the exact timed body (every stream, its workspace and side stream):
     # HIP loads a kernel's code object on its first launch (tens of ms for torch's), which
@@ -342,7 +458,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    accs = run_steps(range(a.steps))
+    accs, last = run_steps(range(a.steps))
     torch.cuda.synchronize()
     if grouped:
         dist.barrier()
@@ -368,30 +484,17 @@ def main():
     value = replicas / el
     ev_rate = local_ev / el
 
-    # the kernels alone (outside the timed region): the roofline's launch duration
-    sms, snl = serial_probe(L, g, pkw, plan["chunk"],
-                            a.probe_steps or (1 if a.workload == "c5" else 3))
+    if a.dump_outputs and rank == 0:   # before anything else runs on the device
+        dump_outputs(a.dump_outputs, *last)
 
-    # roofline of the dominant kernel (the sweep), per launch, this rank
-    n_sweep = max(1, int(nl[1]))
-    sweep_ms = ms[1] / n_sweep
-    sweep_ms_serial = float(sms[1]) if snl[1] else None
     # per LAUNCH: a step runs one launch of each kernel per replica chunk (the engine's
     # pipelined chunks, rq_run_batch), so the step's bytes are split over its launches
+    n_sweep = max(1, int(nl[1]))
+    sweep_ms = ms[1] / n_sweep
     lps = n_sweep / a.steps
     ev_rank = local_ev / world / a.steps / lps
     rows_step = rows_l / a.steps / lps
     posts_step = posts_l / a.steps / lps
-    # the fused sweep (variant >= 10) generates its arrivals in LDS: no arrival reads
-    fused = 10 <= plan["variant"] < 20   # 20+: the fused sweep on merged streams (reads them)
-    merged = not fused and plan["sources_per_lane"] == 0   # rq_merge_streams feeds the sweep
-    b_wall = MRG_SWEEP_B_PER_WALL_EVENT if merged else SWEEP_B_PER_WALL_EVENT
-    sweep_bytes = (0 if fused else b_wall * (ev_rank - posts_step)) + \
-        SWEEP_B_PER_ROW * rows_step
-    achieved_live = sweep_bytes / (sweep_ms * 1e-3) / 1e9
-    # the headline fraction: the kernel's own launch duration (serialised probe); the
-    # overlapped HIP-event time of the timed region is kept as frac_live
-    achieved = sweep_bytes / (sweep_ms_serial * 1e-3) / 1e9 if sweep_ms_serial else achieved_live
     scan_ms = ms[2] / max(1, int(nl[2]))
     gen_ms = ms[0] / max(1, int(nl[0]))
     scan_gbs = SCAN_B_PER_ROW * rows_step / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else None
@@ -401,25 +504,9 @@ def main():
     merge_gbs = MERGE_B_PER_WALL_EVENT * (ev_rank - posts_step) / (merge_ms * 1e-3) / 1e9 \
         if merge_ms > 0 else None
 
-    traffic, traffic_src, issue = pmc_traffic(a.workload, R, plan)
-    if issue and "issue_frac" in issue:
-        # the same ceiling over this run's own HIP-event launch time at the PMC run's clock
-        issue["issue_frac_2400mhz_probe_time"] = issue["valu_insts"] / (
-            N_CU * 4 * 2.4e9 / 2.0 * (sweep_ms_serial or sweep_ms) * 1e-3)
-
-    cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu:
-        nt = min(16, os.cpu_count() or 1)
-        sample = a.cpu_sample or {"c5": 2, "c4": 512}.get(a.workload, 128) * nt
-        cgrid = None
-        if a.workload == "c4":   # 16 grid points spread over the q x s grid
-            from redqueen_amd import graphs
-            cgrid = graphs.c4_grid()[::16]
-        crate, cev, cel = cpu_baseline(so, nt, sample, Ks, cgrid)
-        cpu = {"value": crate, "unit": "replicas/s", "cores": nt, "kind": "port",
-               "sample": "%d %s replicas through the C oracle (engine semantics + Appendix-B "
-                         "metrics), %d pthreads, %.1f s, %.0f events/s" %
-                         (sample, a.workload.upper(), nt, cel, cev)}
+    # --full: the measurements that take runs of their own (every rank runs the probe)
+    extra = full_fields(a, L, g, so, pkw, plan, R, Ks, rank, world, sweep_ms, ev_rank,
+                        rows_step, posts_step) if a.full else {}
 
     if rank == 0:
         line = {
@@ -449,36 +536,9 @@ def main():
             # share the chip: each launch's time is stretched by the overlap)
             "kernels_ms_per_launch": {"gen_streams": gen_ms, "merge_streams": merge_ms, "sweep": sweep_ms,
                                       "scan": scan_ms},
-            # the same launches alone on the chip (serial_probe: pipeline off, one stream)
-            "kernels_ms_per_launch_serial": {"gen_streams": float(sms[0]), "merge_streams": float(sms[4]),
-                                             "sweep": sweep_ms_serial, "scan": float(sms[2]),
-                                             "launches": [int(x) for x in snl]},
             "launches_per_step": lps,
             "caller_streams": len(streams),
             "sweep_plan": plan,
-            "roofline": {"bound": "hbm", "kernel": "rq_sweep", "achieved": achieved,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "duration_ms": sweep_ms_serial or sweep_ms,
-                         "duration_source": "serial_probe: the launch alone on the chip, HIP events"
-                                            if sweep_ms_serial else "timed region, HIP events",
-                         "bytes_per_launch": sweep_bytes,
-                         "achieved_live": achieved_live, "frac_live": achieved_live / HBM_PEAK_GBS,
-                         "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         # what does bound it: SQ issue / wait shares of the wave cycles and
-                         # issue_frac = VALU instructions / the VALU issue ceiling (same PMC run)
-                         "issue": issue,
-                         "issue_frac": issue.get("issue_frac") if issue else None,
-                         "wave_slot_occupancy": issue.get("wave_slot_occupancy") if issue else None,
-                         # the same algorithmic bytes over the launch's duration with every
-                         # kernel serialised (stamped PMC summary, AMD_SERIALIZE_KERNEL=3
-                         # trace): in the timed run the two streams' kernels share the chip,
-                         # which stretches each launch's HIP-event time
-                         "frac_serialized": (sweep_bytes / (issue["serial_avg_ms"] * 1e-3) / 1e9 /
-                                             HBM_PEAK_GBS) if issue and issue.get("serial_avg_ms") else None,
-                         "note": "sweep is latency/issue-bound (serial event chain per replica); "
-                                 "algorithmic bytes = 24 B/pivot row written%s" %
-                                 ("" if fused else " + %d B/wall event read" % b_wall)},
             "scan_gbs": scan_gbs,
             "gen_gbs": gen_gbs,
             "merge_gbs": merge_gbs,
@@ -488,9 +548,9 @@ def main():
                              "peak": HBM_PEAK_GBS, "unit": "GB/s",
                              "frac": e2e_gbs(ev_rate) / HBM_PEAK_GBS / world},
             "exchange": ("RCCL all-gather (process group of %d)" % world) if grouped else None,
-            "cpu_baseline": cpu,
-            "cpu_baseline_reference": ref_cpu_baseline(a.workload),
+            "full": bool(a.full),
         }
+        line.update(extra)
         print(json.dumps(line), flush=True)
     if grouped:
         dist.destroy_process_group()

@@ -24,7 +24,7 @@ for WL in $WLS; do
   find "$ROOT/gpurun_out/pmc_${TAG}_pmc_$WL/kts" -name "*kernel_stats.csv" -exec cp {} "$OUT/${WL}_kernel_stats_serial.csv" \;
   echo "pmc $WL ok"
   CPU=$([ "$WL" = c3 ] && echo "" || echo "--no-cpu")
-  timeout -k 10 400 python3 -u bench.py --workload $WL --steps $S --warmup 2 $CPU > "$OUT/${WL}_bench.log" 2>&1 || { echo "$WL bench failed"; tail -5 "$OUT/${WL}_bench.log"; exit 1; }
+  timeout -k 10 400 python3 -u bench.py --full --workload $WL --steps $S --warmup 2 $CPU > "$OUT/${WL}_bench.log" 2>&1 || { echo "$WL bench failed"; tail -5 "$OUT/${WL}_bench.log"; exit 1; }
   tail -1 "$OUT/${WL}_bench.log" > "$OUT/${WL}_bench.json"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${WL}kt" -o kt -- python3 bench.py --workload $WL --steps $S --warmup 2 --no-cpu > "$OUT/${WL}kt.log" 2>&1 || { echo "$WL kt failed"; tail -5 "$OUT/${WL}kt.log"; exit 1; }
   echo "$WL bench + kt ok"
