@@ -475,7 +475,9 @@ class Graph:
             raise NotImplementedError("more than %d plugin broadcasters" % L.MAX_RD)
         counts = np.zeros((R_all, nrd), dtype=np.int64)
         chunks = []
-        for i in gids:   # increasing: rd_off is a prefix over the global ids
+        # rd_off is a prefix over the global ids: each id once, in increasing order, whatever
+        # the order (or repeats) of a caller's rep_idx
+        for i in np.unique(np.asarray(gids, dtype=np.int64)):
             i = int(i)
             ts = override[i] if override is not None else \
                 [self._plugin_source_times(inst)
@@ -576,8 +578,9 @@ class Graph:
         me = kw.get("max_events")
         me = None if me is None or me == float("inf") else int(me)
         ctrl = args[0] if args else kw.get("ctrl", "opt")
+        ck = CTRL_BY_NAME[ctrl] if isinstance(ctrl, str) else int(ctrl)
         static_ids = set(self.static_src_ids)
-        if ctrl in ("poisson", "pwconst", "times"):
+        if ck in (L.SRC_POISSON2, L.SRC_PWCONST, L.SRC_REALDATA):
             static_ids.add(self.src_id)   # a static controlled source (Poisson2 / PWConst / RealData)
 
         def make(i):

@@ -317,3 +317,59 @@ def test_reactive_plugin_equal_time_order(golden):
     c = res.counts.cpu().numpy()
     assert np.array_equal(mm, d["rand_met"]), mm - d["rand_met"]
     assert np.array_equal(c[:, :3], d["rand_cnt"])
+
+
+def _same_rows(full, part, rows):
+    """Outputs of ``part`` equal rows ``rows`` of ``full`` bit for bit (events too)."""
+    import torch
+    at = torch.as_tensor(rows, device=full.metrics.device)
+    assert torch.equal(part.metrics, full.metrics[at]) and torch.equal(part.counts, full.counts[at])
+    assert torch.equal(part.status, full.status[at])
+    assert list(part.global_ids) == list(rows)
+    for k, r in enumerate(rows):
+        (ta, sa), (tb, sb) = part.events(k), full.events(r)
+        assert np.array_equal(ta, tb) and np.array_equal(sa, sb), (k, r)
+
+
+@pytest.mark.parametrize("rep_idx", [[2, 5], [5, 2], [2, 2], [7, 0, 7, 3]])
+def test_rep_idx_any_order_with_randomized_plugin(rep_idx):
+    """Graph.run(rep_idx=...) with a randomized static plugin: the per-replica plugin
+    times are laid out by global id whatever the order of the list, so an unsorted or
+    repeated list gives exactly those rows of the full batch (it used to hand replicas
+    each other's times)."""
+    engine, SimOpts, Bursty, (w, ctrl, us) = _setup()
+    g = engine.Graph(w["src_id"], w["other_sources"], w["sink_ids"], w["edge_list"],
+                     w["end_time"], ctrl_a=ctrl)
+    kw = dict(n_rep=len(us), world_seed=0, randomize=True, Ks=KS, event_log=True)
+    full = g.run("times", **kw)
+    assert len({int(x) for x in full.counts[:, 2].tolist()}) > 4   # the replicas do differ
+    _same_rows(full, g.run("times", rep_idx=rep_idx, **kw), rep_idx)
+
+
+@pytest.mark.parametrize("kind", ["poisson", "SRC_POISSON2"])
+def test_reactive_plugin_static_controller_by_name_or_kind(kind, monkeypatch):
+    """A reactive dynamic plugin beside a Poisson2 (static) controlled source, the
+    controller given by name or by its integer kind: the host fixed point orders equal
+    times against the controller as a static source either way (static_ids holds it),
+    and both spellings give the same batch."""
+    engine, SimOpts, (w, ctrl, us) = _dyn_setup()
+    from redqueen_amd import _lib as L
+    from redqueen_amd import opt_model
+    w2 = _knock_world(w)
+    seen = []
+    real = opt_model.reactive_plugin_times
+
+    def spy(*a, **k):
+        seen.append(set(k.get("static_ids", ())))
+        return real(*a, **k)
+    monkeypatch.setattr(opt_model, "reactive_plugin_times", spy)
+    kw = dict(n_rep=8, ctrl_seed=5, world_seed=0, randomize=True, ctrl_rate=0.7, Ks=KS, event_log=True)
+
+    def run(c):
+        g = engine.Graph(w2["src_id"], w2["other_sources"], w2["sink_ids"], w2["edge_list"], w2["end_time"])
+        res = g.run(c, **kw)
+        assert g.reactive_reruns >= 1
+        return res
+    res = run(L.SRC_POISSON2 if kind == "SRC_POISSON2" else kind)
+    assert seen and all(w2["src_id"] in s and 6 in s for s in seen), seen[:2]
+    _same_rows(run("poisson"), res, list(range(8)))
