@@ -351,7 +351,38 @@ double ws_budget(const rq_batch_desc* b, double fallback)
     return bud;
 }
 
-int make_plan(const rq_graph* g, const rq_batch_desc* b, Plan* p, double budget)
+// The sweep instance of a plan -- or of a candidate the LDS searches of make_plan score:
+// what a search is still deciding (sweep kind, ring depth, column placement, GS, GT) comes
+// as arguments, the rest from the plan so far.
+SweepInst sweep_inst(const Plan& p, int ctrl_kind, bool fused, int W, bool col16, bool gs, bool gt)
+{
+    SweepInst i{};
+    i.fused = fused;
+    i.nK = p.nK;
+    i.col16 = col16;
+    i.log = p.log;
+    i.gs = gs;
+    i.bits = p.bits;
+    i.bl = p.bl;
+    i.mrg = fused ? p.fwm : p.mrg;
+    i.spl = p.spl;
+    i.W = W;
+    i.gt = gt;
+    i.pw = ctrl_kind == RQ_SRC_OPTPW;   // exactly the runs rq_run_batch gives SweepArgs.pw_c
+    return i;
+}
+// the instance a finished plan runs
+SweepInst sweep_inst(const Plan& p, int ctrl_kind)
+{
+    return sweep_inst(p, ctrl_kind, p.fw, p.gwin, p.gcol16, p.gs, p.gt);
+}
+int sweep_blocks_per_cu(const SweepInst& i, int wpb, size_t lds)
+{
+    return i.fused ? rq_fw_blocks_per_cu(i, wpb, lds) : rq_sweep_blocks_per_cu(i, wpb, lds);
+}
+
+// make_plan, part 1: the call's arguments, its replica window and per-replica RealData
+int plan_args(const rq_graph* g, const rq_batch_desc* b, Plan* p)
 {
     if (!g || !b) return RQ_EINVAL;
     if (b->nK < 1 || b->nK > RQ_MAX_K || !b->Ks) return RQ_EINVAL;
@@ -366,7 +397,6 @@ int make_plan(const rq_graph* g, const rq_batch_desc* b, Plan* p, double budget)
         return RQ_EINVAL;
     if (ck == RQ_SRC_POISSON2 && !b->ctrl_rate) return RQ_EINVAL;
     if ((ck == RQ_SRC_PWCONST) && g->ctrl_arr_n < 1) return RQ_EINVAL;
-    const double scale = b->cap_scale >= 1.0 ? b->cap_scale : 1.0;
     p->nK = b->nK;
     // the call's replica space: the [rep_lo, rep_lo + rep_cnt) window of every grid point
     if (b->rep_cnt < 0 || (b->rep_cnt > 0 && (b->rep_lo < 0 || b->rep_lo + b->rep_cnt > b->n_rep)))
@@ -402,6 +432,14 @@ int make_plan(const rq_graph* g, const rq_batch_desc* b, Plan* p, double budget)
             p->rd_k[jk] = k;
         }
     }
+    return RQ_OK;
+}
+
+// make_plan, part 2: per-stream, merged-sequence and pivot-row capacities
+int plan_capacities(const rq_graph* g, const rq_batch_desc* b, Plan* p)
+{
+    const int ck = b->ctrl_kind;
+    const double scale = b->cap_scale >= 1.0 ? b->cap_scale : 1.0;
     double wall_caps = 0.0, wall_mean = 0.0, wall_var = 0.0;
     int64_t ctrl_cap = 0;
     for (int j = 0; j < g->n_str; ++j) {
@@ -448,33 +486,13 @@ int make_plan(const rq_graph* g, const rq_batch_desc* b, Plan* p, double budget)
     if (b->max_events >= 0) rows = std::min(rows, (double)b->max_events + 1.0);
     // a multiple of 32 rows: replica row bases stay aligned to the scan's 32-row trips
     p->cap_rows = (std::max<int64_t>(64, (int64_t)rows) + 31) & ~(int64_t)31;
-    // Opt / OptPWSignificance with a duplicated controlled edge: the reference's follower
-    // vectors (sqrt_s_by_q, old_ranks: one entry per edge) no longer match the ranks (one
-    // per distinct follower) and its first non-own event raises ValueError
-    if (g->ctrl_dup && (ck == RQ_SRC_OPT || ck == RQ_SRC_OPTPW)) return RQ_EINVAL;
-    if (g->n_str > RQ_MAX_STREAMS_MRG) return RQ_EUNSUPPORTED;
-    p->spl = g->n_str <= 64 ? 1 : g->n_str <= 128 ? 2 : g->n_str <= 256 ? 4 : 8;
-    p->n_sinks_pad = (g->n_sinks + 1) | 1;   // odd stride: spreads replicas over LDS banks
-    const size_t per_wave = (size_t)p->n_sinks_pad * 4;
-    p->wpb = per_wave * 4 <= 64 * 1024 ? 4 : per_wave * 2 <= 80 * 1024 ? 2 : 1;
+    return RQ_OK;
+}
 
-    // the sequential exact variant when equal event times are certain: the graph's own
-    // RealData times (every replica plays them) repeat a time; otherwise RealData and
-    // the per-replica plugin streams play on the fast sweeps, which flag RQ_ST_TIE on any
-    // equal-time pair, and the caller reruns the flagged replicas on the exact sequential
-    // sweep (rq_batch_desc.rep_idx).  max_events cuts the fast sweeps' tiles
-    // (truncate_tile); the fast sweeps write the event log themselves.
-    const bool rd_ties = ck == RQ_SRC_REALDATA ? g->rd_ties_ctrl : g->rd_ties;
-    p->log = b->sweep_mode == 2 || (rd_ties && b->sweep_mode != 1 && b->sweep_mode != 5);
-    for (int q = 0; q < b->nK; ++q) p->log = p->log || b->Ks[q] > 32767;   // int16 ranks
-    // a multigraph (duplicate edges make fractional pivot cells, the exact sequential
-    // sweep's business); > 512 sources: the fast general sweep plays the two-level merged
-    // sequence (rq_merge_streams per group of 512, then over the groups), the windowed
-    // sweep (mode 6) owns <= 8 sources per lane
-    p->log = p->log || g->multi || (g->n_str > 512 && b->sweep_mode == 6);
-    const int nwl = (g->n_sinks + 31) / 32;
-
-  replan:
+// the sweep variant of a make_plan pass, p->log decided: sources per lane, K = 1 sink
+// bits, merged streams and the merge's groups
+void plan_variant(const rq_graph* g, const rq_batch_desc* b, Plan* p)
+{
     // the sequential sweep owns <= 32 sources per lane; past that it plays the merged
     // (t, stream) sequence of rq_merge_streams like the fast general sweep
     p->lmrg = p->log && g->n_str > RQ_MAX_STREAMS;
@@ -503,121 +521,116 @@ int make_plan(const rq_graph* g, const rq_batch_desc* b, Plan* p, double budget)
         p->grp_sz = atoi(e) == 64 && g->n_str <= 64 * 64 ? 64 : RQ_MG_B;
     p->n_grp = g->n_str > RQ_MG_B ? (g->n_str + p->grp_sz - 1) / p->grp_sz : 1;
     if (const char* e = getenv("RQ_MRG")) p->mrg = p->lmrg || (p->mrg && atoi(e) != 0);   // A/B only
-    // without the merged streams the windowed sweep owns <= 8 sources per lane
-    if (!p->mrg && !p->log && g->n_str > 512) {
-        p->log = true;
-        goto replan;
-    }
+}
 
-    // general sweep: pick (ring depth W, waves per block) for the most waves per CU
-    {
-        int best = -1;
-        // sink columns live in LDS as uint16 when they fit, else they are read from
-        // global memory as int (the kernel's COL type selects the path at compile time)
-        // both placements are scored: LDS columns only win at equal waves per CU
-        // LOG: the per-sink state in LDS, or (gs) in global memory for more sinks than fit
-        // GT (merged streams only): the per-stream tables in global memory -- tried when no
-        // layout with them in LDS fits, always for the sequential sweep on merged streams
-        for (int gt = p->lmrg ? 1 : 0; gt <= (p->mrg ? 1 : 0) && best < 0; ++gt)
-        for (int gs = 0; gs <= (p->log ? 1 : 0); ++gs)
-        for (int col_lds = g->n_sinks <= 65535 && !(p->log && p->spl >= 16) && !gt ? 1 : 0; col_lds >= 0; --col_lds) {
-            if (gt && p->bits) continue;   // the sink-bitset instances keep their tables in LDS
-            if (const char* e = getenv("RQ_G_COLLDS"))   // tuning only: force the column placement
-                if (atoi(e) != col_lds) continue;
-            const int c16 = col_lds;
-            // BITS: sink bitsets [n_str][nw] replace the columns (and the per-wave ranks)
-            const size_t colb = p->bits ? 4 * (size_t)g->n_str * p->mstride
-                                        : (col_lds ? 2 * g->csr_col.size() : 0);
-            size_t sh = 0;
-            const size_t o_col = sh;  sh = align_up(sh + colb, 16);
-            const size_t tabn = gt ? 0 : (size_t)g->n_str;
-            const size_t o_ptr = sh;  sh = align_up(sh + 4 * (tabn + (gt ? 0 : 1)), 16);
-            const size_t o_odf = sh;  sh = align_up(sh + 4 * tabn, 16);
-            const size_t o_cbf = sh;  sh = align_up(sh + 4 * tabn, 16);
-            const size_t o_fb = sh;   if (p->bl) sh = align_up(sh + 4 * (size_t)nwl, 16);
-            // one grid point: the 1/c_j table once per block instead of once per wave
-            const bool inv_sh = b->n_grid == 1 && !gt;
-            const size_t o_inv = sh;  if (inv_sh) sh = align_up(sh + 8 * (size_t)g->n_str, 16);
-            const int spl = p->spl;
-            int only_w = 0;
-            if (const char* e = getenv("RQ_G_W")) only_w = atoi(e);   // tuning only
-            // LOG: LDS rings of W = 8 per source (4 at 32 sources per lane); the fast sweep:
-            // a register window of 4
-            for (int W : {8, 4}) {
-                if ((p->log ? (spl >= 32 ? 4 : 8) : 4) != W) continue;
-                if (only_w && W != only_w) continue;
-                const size_t r_off = inv_sh || gt ? 0 : align_up(8 * (size_t)g->n_str, 16);
-                const size_t rank_b = p->log ? (gs ? 0 : 4) : (p->bits ? 0 : 2);   // fast: int16 saturating
-            const int spl_i = p->mrg ? (gt ? -1 : 0) : spl;   // the instance: 0 = merged streams, -1 with GT
-                // BL: two bits per sink (T, V words) in place of the int16 ranks
-                const size_t w_off = p->bl ? align_up(r_off + 8 * (size_t)nwl, 16)
-                                           : align_up(r_off + rank_b * (size_t)p->n_sinks_pad, 16);
-                // LOG: rings of W arrivals for each real source; fast: the tile's staging
-                size_t stride = p->log && !p->lmrg ? align_up(w_off + 8 * (size_t)g->n_str * W, 16)
-                                                   : align_up(w_off + 64 * 12, 16);
-                // LOG: per-sink gtag/gcnt/gsum (gs: in global memory) + a wave_npsum<1>
-                // scratch (RQ_NPSUM1_LDS doubles)
-                const size_t x_off = stride;
-                if (p->log) stride = align_up(x_off + (gs ? 0 : 12 * (size_t)p->n_sinks_pad) + 8 * (size_t)RQ_NPSUM1_LDS, 16);
-                for (int wpb : {16, 12, 10, 8, 6, 5, 4, 3, 2, 1}) {
-                    if (p->log && wpb > 4) continue;   // LOG instances: 256-thread blocks
-                    if (!p->log && !p->mrg && spl >= 4 && wpb > 8) continue;   // 512-thread instances
-                    if (p->mrg && 64 * wpb > RQ_MRG_LB) continue;
-                    const size_t tot = sh + wpb * stride;
-                    if (tot > kLdsMax) continue;
-                    // resident waves per CU: the runtime's occupancy for this instance
-                    // (VGPR/SGPR/LDS); without a device, the LDS bound capped at 16
-                    int blocks = rq_sweep_blocks_per_cu(spl_i, p->nK, c16, W, p->log ? 1 + gs : 0,
-                                                        p->bl ? 2 : p->bits, wpb, tot);
-                    if (blocks <= 0) blocks = (int)std::min<size_t>(kLdsMax / tot, 16 / wpb);
-                    const int waves = blocks * wpb;
-                    // LDS columns skip the global latency; LDS sink state wherever it fits
-                    const int score = waves * 8 + col_lds * 2 + (gs ? 0 : 100000);
-                    if (score > best) {
-                        best = score;
-                        p->wpc = waves;
-                        p->gs = gs;
-                        p->gs_slots = std::min<int64_t>((int64_t)align_up((size_t)p->chunk, (size_t)wpb),
-                                                        (int64_t)blocks * wpb * rq_cu_count());
-                        p->gwin = W; p->gwpb = wpb; p->gcol_lds = col_lds; p->gcol16 = c16;
-                        p->g_col = o_col; p->g_ptr = o_ptr; p->g_odf = o_odf; p->g_cbf = o_cbf;
-                        p->g_wave = sh; p->g_wave_stride = stride; p->g_rank_off = r_off;
-                        p->g_win_off = w_off; p->g_x_off = x_off; p->g_total = tot; p->g_fb = o_fb;
-                        p->g_inv = o_inv; p->g_inv_sh = inv_sh; p->gt = gt;
-                    }
+// general sweep: pick (ring depth W, waves per block) for the most waves per CU; false:
+// no layout of this variant fits LDS
+bool plan_general_lds(const rq_graph* g, const rq_batch_desc* b, Plan* p)
+{
+    const int nwl = (g->n_sinks + 31) / 32;
+    int best = -1;
+    // sink columns live in LDS as uint16 when they fit, else they are read from
+    // global memory as int (the kernel's COL type selects the path at compile time)
+    // both placements are scored: LDS columns only win at equal waves per CU
+    // LOG: the per-sink state in LDS, or (gs) in global memory for more sinks than fit
+    // GT (merged streams only): the per-stream tables in global memory -- tried when no
+    // layout with them in LDS fits, always for the sequential sweep on merged streams
+    for (int gt = p->lmrg ? 1 : 0; gt <= (p->mrg ? 1 : 0) && best < 0; ++gt)
+    for (int gs = 0; gs <= (p->log ? 1 : 0); ++gs)
+    for (int col_lds = g->n_sinks <= 65535 && !(p->log && p->spl >= 16) && !gt ? 1 : 0; col_lds >= 0; --col_lds) {
+        if (gt && p->bits) continue;   // the sink-bitset instances keep their tables in LDS
+        if (const char* e = getenv("RQ_G_COLLDS"))   // tuning only: force the column placement
+            if (atoi(e) != col_lds) continue;
+        const int c16 = col_lds;
+        // BITS: sink bitsets [n_str][nw] replace the columns (and the per-wave ranks)
+        const size_t colb = p->bits ? 4 * (size_t)g->n_str * p->mstride
+                                    : (col_lds ? 2 * g->csr_col.size() : 0);
+        size_t sh = 0;
+        const size_t o_col = sh;  sh = align_up(sh + colb, 16);
+        const size_t tabn = gt ? 0 : (size_t)g->n_str;
+        const size_t o_ptr = sh;  sh = align_up(sh + 4 * (tabn + (gt ? 0 : 1)), 16);
+        const size_t o_odf = sh;  sh = align_up(sh + 4 * tabn, 16);
+        const size_t o_cbf = sh;  sh = align_up(sh + 4 * tabn, 16);
+        const size_t o_fb = sh;   if (p->bl) sh = align_up(sh + 4 * (size_t)nwl, 16);
+        // one grid point: the 1/c_j table once per block instead of once per wave
+        const bool inv_sh = b->n_grid == 1 && !gt;
+        const size_t o_inv = sh;  if (inv_sh) sh = align_up(sh + 8 * (size_t)g->n_str, 16);
+        const int spl = p->spl;
+        int only_w = 0;
+        if (const char* e = getenv("RQ_G_W")) only_w = atoi(e);   // tuning only
+        // LOG: LDS rings of W = 8 per source (4 at 32 sources per lane); the fast sweep:
+        // a register window of 4
+        for (int W : {8, 4}) {
+            if ((p->log ? (spl >= 32 ? 4 : 8) : 4) != W) continue;
+            if (only_w && W != only_w) continue;
+            const size_t r_off = inv_sh || gt ? 0 : align_up(8 * (size_t)g->n_str, 16);
+            const size_t rank_b = p->log ? (gs ? 0 : 4) : (p->bits ? 0 : 2);   // fast: int16 saturating
+            const SweepInst inst = sweep_inst(*p, b->ctrl_kind, false, W, c16, gs, gt);
+            // BL: two bits per sink (T, V words) in place of the int16 ranks
+            const size_t w_off = p->bl ? align_up(r_off + 8 * (size_t)nwl, 16)
+                                       : align_up(r_off + rank_b * (size_t)p->n_sinks_pad, 16);
+            // LOG: rings of W arrivals for each real source; fast: the tile's staging
+            size_t stride = p->log && !p->lmrg ? align_up(w_off + 8 * (size_t)g->n_str * W, 16)
+                                               : align_up(w_off + 64 * 12, 16);
+            // LOG: per-sink gtag/gcnt/gsum (gs: in global memory) + a wave_npsum<1>
+            // scratch (RQ_NPSUM1_LDS doubles)
+            const size_t x_off = stride;
+            if (p->log) stride = align_up(x_off + (gs ? 0 : 12 * (size_t)p->n_sinks_pad) + 8 * (size_t)RQ_NPSUM1_LDS, 16);
+            for (int wpb : {16, 12, 10, 8, 6, 5, 4, 3, 2, 1}) {
+                if (p->log && wpb > 4) continue;   // LOG instances: 256-thread blocks
+                if (!p->log && !p->mrg && spl >= 4 && wpb > 8) continue;   // 512-thread instances
+                if (p->mrg && 64 * wpb > RQ_MRG_LB) continue;
+                const size_t tot = sh + wpb * stride;
+                if (tot > kLdsMax) continue;
+                // resident waves per CU: the runtime's occupancy for this instance
+                // (VGPR/SGPR/LDS); without a device, the LDS bound capped at 16
+                int blocks = sweep_blocks_per_cu(inst, wpb, tot);
+                if (blocks <= 0) blocks = (int)std::min<size_t>(kLdsMax / tot, 16 / wpb);
+                const int waves = blocks * wpb;
+                // LDS columns skip the global latency; LDS sink state wherever it fits
+                const int score = waves * 8 + col_lds * 2 + (gs ? 0 : 100000);
+                if (score > best) {
+                    best = score;
+                    p->wpc = waves;
+                    p->gs = gs;
+                    p->gs_slots = std::min<int64_t>((int64_t)align_up((size_t)p->chunk, (size_t)wpb),
+                                                    (int64_t)blocks * wpb * rq_cu_count());
+                    p->gwin = W; p->gwpb = wpb; p->gcol_lds = col_lds; p->gcol16 = c16;
+                    p->g_col = o_col; p->g_ptr = o_ptr; p->g_odf = o_odf; p->g_cbf = o_cbf;
+                    p->g_wave = sh; p->g_wave_stride = stride; p->g_rank_off = r_off;
+                    p->g_win_off = w_off; p->g_x_off = x_off; p->g_total = tot; p->g_fb = o_fb;
+                    p->g_inv = o_inv; p->g_inv_sh = inv_sh; p->gt = gt;
                 }
             }
         }
-        if (best < 0) {
-            if (p->log) return RQ_EUNSUPPORTED;
-            p->log = true;   // no fast instance fits this graph: the exact sequential sweep
-            goto replan;
-        }
-        // stream ids past 16 bits are read (mrg_jh) by the GT instances only; such graphs'
-        // tables never fit LDS, so they always get one
-        if (p->mrg && g->n_str > 65535 && !p->gt) return RQ_EUNSUPPORTED;
-        // BL on merged streams: a per-wave stamp (the reset epoch a stream last played in)
-        // and first-lane table per stream let a tile skip the events whose stream already
-        // played since the last post -- their sinks are out of the top-1 set and valid.
-        // Only where it costs no resident waves.
-        p->g_skip = 0;
-        if (p->bl && p->mrg && !p->gs) {
-            const size_t st2 = align_up(p->g_wave_stride + 8 * (size_t)g->n_str, 16);
-            const size_t tot2 = p->g_wave + p->gwpb * st2;
-            int blocks = tot2 <= kLdsMax ? rq_sweep_blocks_per_cu(p->gt ? -1 : 0, p->nK, p->gcol16, p->gwin, 0, 2, p->gwpb, tot2) : 0;
-            if (tot2 <= kLdsMax && blocks <= 0) blocks = (int)std::min<size_t>(kLdsMax / tot2, 16 / p->gwpb);
-            bool on = blocks * p->gwpb >= p->wpc;
-            if (const char* e = getenv("RQ_SKIP")) on = on && atoi(e) != 0;   // A/B only
-            if (on) {
-                p->g_skip = p->g_wave_stride;
-                p->g_wave_stride = st2;
-                p->g_total = tot2;
-            }
+    }
+    if (best < 0) return false;
+    // BL on merged streams: a per-wave stamp (the reset epoch a stream last played in)
+    // and first-lane table per stream let a tile skip the events whose stream already
+    // played since the last post -- their sinks are out of the top-1 set and valid.
+    // Only where it costs no resident waves.
+    p->g_skip = 0;
+    if (p->bl && p->mrg && !p->gs) {
+        const size_t st2 = align_up(p->g_wave_stride + 8 * (size_t)g->n_str, 16);
+        const size_t tot2 = p->g_wave + p->gwpb * st2;
+        const SweepInst inst = sweep_inst(*p, b->ctrl_kind, false, p->gwin, p->gcol16, p->gs, p->gt);
+        int blocks = tot2 <= kLdsMax ? sweep_blocks_per_cu(inst, p->gwpb, tot2) : 0;
+        if (tot2 <= kLdsMax && blocks <= 0) blocks = (int)std::min<size_t>(kLdsMax / tot2, 16 / p->gwpb);
+        bool on = blocks * p->gwpb >= p->wpc;
+        if (const char* e = getenv("RQ_SKIP")) on = on && atoi(e) != 0;   // A/B only
+        if (on) {
+            p->g_skip = p->g_wave_stride;
+            p->g_wave_stride = st2;
+            p->g_total = tot2;
         }
     }
+    return true;
+}
 
-    // fused windowed sweep: one stream per lane, rings of W arrivals generated in LDS,
-    // a window of H per ring in registers; (W, H, waves per block) for the most waves per CU
+// fused windowed sweep: one stream per lane, rings of W arrivals generated in LDS,
+// a window of H per ring in registers; (W, H, waves per block) for the most waves per CU
+void plan_fused_lds(const rq_graph* g, const rq_batch_desc* b, Plan* p)
+{
     const bool pw = b->ctrl_kind == RQ_SRC_OPTPW;
     p->fw = !p->log && !p->bl && g->n_str <= 64 && b->sweep_mode != 4 && b->sweep_mode != 5 &&
             b->sweep_mode != 6;
@@ -654,7 +667,7 @@ int make_plan(const rq_graph* g, const rq_batch_desc* b, Plan* p, double budget)
             for (int wpb : {16, 12, 10, 8, 6, 5, 4, 3, 2, 1}) {
                 const size_t tot = sh + wpb * stride;
                 if (tot > kLdsMax) continue;
-                int blocks = rq_fw_blocks_per_cu(p->nK, c16, p->fwm ? 0 : W, p->bits, wpb, tot, pw);
+                int blocks = sweep_blocks_per_cu(sweep_inst(*p, b->ctrl_kind, true, W, c16, false, false), wpb, tot);
                 if (blocks <= 0) blocks = (int)std::min<size_t>(kLdsMax / tot, 16 / wpb);
                 const int waves = blocks * wpb;
                 const int score = waves * 4 + (W == 16 ? 2 : W == 32 ? 1 : 0);
@@ -673,6 +686,52 @@ int make_plan(const rq_graph* g, const rq_batch_desc* b, Plan* p, double budget)
     }
     if (!p->fw) p->fwm = false;
     if (p->fw) p->mrg = p->fwm;   // the merge kernel feeds the fused sweep too
+}
+
+int make_plan(const rq_graph* g, const rq_batch_desc* b, Plan* p, double budget)
+{
+    if (const int rc = plan_args(g, b, p)) return rc;
+    if (const int rc = plan_capacities(g, b, p)) return rc;
+    const int ck = b->ctrl_kind;
+    // Opt / OptPWSignificance with a duplicated controlled edge: the reference's follower
+    // vectors (sqrt_s_by_q, old_ranks: one entry per edge) no longer match the ranks (one
+    // per distinct follower) and its first non-own event raises ValueError
+    if (g->ctrl_dup && (ck == RQ_SRC_OPT || ck == RQ_SRC_OPTPW)) return RQ_EINVAL;
+    if (g->n_str > RQ_MAX_STREAMS_MRG) return RQ_EUNSUPPORTED;
+    p->spl = g->n_str <= 64 ? 1 : g->n_str <= 128 ? 2 : g->n_str <= 256 ? 4 : 8;
+    p->n_sinks_pad = (g->n_sinks + 1) | 1;   // odd stride: spreads replicas over LDS banks
+    const size_t per_wave = (size_t)p->n_sinks_pad * 4;
+    p->wpb = per_wave * 4 <= 64 * 1024 ? 4 : per_wave * 2 <= 80 * 1024 ? 2 : 1;
+
+    // the sequential exact variant when equal event times are certain: the graph's own
+    // RealData times (every replica plays them) repeat a time; otherwise RealData and
+    // the per-replica plugin streams play on the fast sweeps, which flag RQ_ST_TIE on any
+    // equal-time pair, and the caller reruns the flagged replicas on the exact sequential
+    // sweep (rq_batch_desc.rep_idx).  max_events cuts the fast sweeps' tiles
+    // (truncate_tile); the fast sweeps write the event log themselves.
+    const bool rd_ties = ck == RQ_SRC_REALDATA ? g->rd_ties_ctrl : g->rd_ties;
+    p->log = b->sweep_mode == 2 || (rd_ties && b->sweep_mode != 1 && b->sweep_mode != 5);
+    for (int q = 0; q < b->nK; ++q) p->log = p->log || b->Ks[q] > 32767;   // int16 ranks
+    // a multigraph (duplicate edges make fractional pivot cells, the exact sequential
+    // sweep's business); > 512 sources: the fast general sweep plays the two-level merged
+    // sequence (rq_merge_streams per group of 512, then over the groups), the windowed
+    // sweep (mode 6) owns <= 8 sources per lane
+    p->log = p->log || g->multi || (g->n_str > 512 && b->sweep_mode == 6);
+
+    // a graph no fast instance takes goes to the exact sequential sweep: one further pass
+    // with p->log set; a sequential pass that fits nothing ends the loop
+    for (;;) {
+        plan_variant(g, b, p);
+        // without the merged streams the windowed sweep owns <= 8 sources per lane
+        const bool too_wide = !p->mrg && !p->log && g->n_str > 512;
+        if (!too_wide && plan_general_lds(g, b, p)) break;
+        if (p->log) return RQ_EUNSUPPORTED;
+        p->log = true;
+    }
+    // stream ids past 16 bits are read (mrg_jh) by the GT instances only; such graphs'
+    // tables never fit LDS, so they always get one
+    if (p->mrg && g->n_str > 65535 && !p->gt) return RQ_EUNSUPPORTED;
+    plan_fused_lds(g, b, p);
 
     // pipelined chunks for the merged-stream sweeps (not the sequential LOG sweep, whose
     // global per-sink slots are sized for one grid): the batch in an even number of
@@ -1090,10 +1149,7 @@ int rq_plan_info(rq_graph_t g, const rq_batch_desc* b, int64_t* info)
     info[1] = p.mrg ? 0 : p.spl;   // 0: merged streams (lanes own no sources)
     info[2] = p.gwin;
     info[3] = p.gwpb;
-    info[4] = p.fw ? rq_fw_blocks_per_cu(p.nK, p.gcol16, p.fwm ? 0 : p.gwin, p.bits, p.gwpb, p.g_total,
-                                          b->ctrl_kind == RQ_SRC_OPTPW)
-                   : rq_sweep_blocks_per_cu(p.mrg ? (p.gt ? -1 : 0) : p.spl, p.nK, p.gcol16, p.gwin, p.log ? 1 + p.gs : 0,
-                                            p.bl ? 2 : p.bits, p.gwpb, p.g_total);
+    info[4] = sweep_blocks_per_cu(sweep_inst(p, b->ctrl_kind), p.gwpb, p.g_total);
     info[5] = p.gcol_lds;
     info[6] = (int64_t)p.g_total;
     info[7] = p.chunk;
@@ -1462,9 +1518,8 @@ int rq_run_batch(rq_graph_t g, const rq_batch_desc* b, const rq_outputs* out, vo
                 sa.wq = (int*)(wsb + p.off_wq);
             }
             TimedLaunch tl(K_SWEEP, s);
-            const hipError_t e = p.fw ? rq_launch_sweep_fw(sa, p.nK, p.gcol16, p.fwm ? 0 : p.gwin, p.bits, s)
-                                      : rq_launch_sweep(sa, p.mrg ? (p.gt ? -1 : 0) : p.spl, p.nK, p.gcol16, p.log ? 1 + p.gs : 0,
-                                                        p.bl ? 2 : p.bits, s);
+            const SweepInst inst = sweep_inst(p, b->ctrl_kind);
+            const hipError_t e = inst.fused ? rq_launch_sweep_fw(sa, inst, s) : rq_launch_sweep(sa, inst, s);
             if (e != hipSuccess) return RQ_EHIP;
         }
 

@@ -204,13 +204,36 @@ struct ScanArgs {
     int* wq;                // replica work queue (zeroed before the launch; null = one replica per wave)
 };
 
+// The sweep template instance a plan selects, one field per template axis.  rq_api.cpp
+// builds it from a Plan (sweep_inst: the planner's candidates, rq_plan_info and the
+// launch alike); each kernel file resolves it to the kernel in one place (sweep_kernel /
+// fw_kernel), which the launch and the occupancy query share.  The flags name the kernels'
+// template parameters (rq_kernels.hip, rq_sweep_fw.hip).
+struct SweepInst {
+    bool fused;   // rq_sweep_fw / rq_sweep_fwm (<= 64 sources), else the general rq_sweep
+    int nK;       // K variants (1..RQ_MAX_K)
+    bool col16;   // sink columns in LDS as uint16, else read from global memory as int
+    bool log;     // the sequential sweep (event log, max_events, duplicate edges, ties)
+    bool gs;      // log: the per-sink state in global memory (SweepArgs.gs)
+    bool bits;    // K = 1 on per-stream sink bitsets
+    bool bl;      // K = 1 on per-wave LDS sink bits (general sweep)
+    bool mrg;     // plays the merged streams of rq_merge_streams; else:
+    int spl;      //   general: sources per lane, 1 / 2 / 4 / 8 (log: 1 / 8 / 16 / 32)
+    int W;        //   fused: depth of the generated arrival rings, 32 / 16 / 8 (the general
+                  //   instances fix theirs: a window of 4; log: rings of 8, 4 at 32 per lane)
+    bool gt;      // mrg, general: the per-stream tables in global memory
+    bool pw;      // fused: the OptPWSignificance controller
+};
+using SweepKernel = void (*)(SweepArgs);
+
 hipError_t rq_launch_gen(const GenArgs& a, hipStream_t s);
-// log: 0 fast tiled sweep, 1 sequential (LOG) sweep, 2 LOG with the per-sink state in
-// global memory (SweepArgs.gs)
-hipError_t rq_launch_sweep(const SweepArgs& a, int spl, int nK, int col16, int log, int bits, hipStream_t s);
+// hipErrorInvalidValue for a combination without an instance (bits with gt; fused: pw
+// with merged streams, without uint16 columns or at W != 16)
+hipError_t rq_launch_sweep(const SweepArgs& a, const SweepInst& i, hipStream_t s);
 hipError_t rq_launch_scan(const ScanArgs& a, int nK, hipStream_t s);
-int rq_sweep_blocks_per_cu(int spl, int nK, int col16, int W, int log, int bits, int wpb, size_t lds);
-// spl = 0 in rq_launch_sweep / rq_sweep_blocks_per_cu: the fast sweep reading merged streams
+// blocks of 64 * wpb threads per CU the instance reaches with `lds` bytes of dynamic LDS
+// (rq_occupancy); <= 0: no instance or no device -- the planner takes the LDS bound
+int rq_sweep_blocks_per_cu(const SweepInst& i, int wpb, size_t lds);
 hipError_t rq_launch_merge(const MergeArgs& a, hipStream_t s);
 // > RQ_MG_B sources: level 1 over n_grp groups (a.n_str streams, grid C x n_grp), then
 // the second level over the groups' sequences (a.sub_*, a.n_grp "streams")
@@ -221,8 +244,9 @@ hipError_t rq_launch_merge_sub(const MergeArgs& a, hipStream_t s);
 #define RQ_MAX_STREAMS_MRG (RQ_MG_B * RQ_MG_B)
 // longest-first order of n <= 65536 replicas by len (descending; ties in any order)
 hipError_t rq_launch_order(const int* len, int64_t n, int* order, hipStream_t s);
-hipError_t rq_launch_sweep_fw(const SweepArgs& a, int nK, int col16, int W, int bits, hipStream_t s);
-int rq_fw_blocks_per_cu(int nK, int col16, int W, int bits, int wpb, size_t lds, int pw);
+// the fused pair of rq_launch_sweep / rq_sweep_blocks_per_cu (SweepInst.fused)
+hipError_t rq_launch_sweep_fw(const SweepArgs& a, const SweepInst& i, hipStream_t s);
+int rq_fw_blocks_per_cu(const SweepInst& i, int wpb, size_t lds);
 int rq_cu_count();   // CUs of the current device (256 on MI355X when the query fails)
 
 // Blocks per CU a kernel reaches at `threads` threads and `lds` bytes of dynamic LDS

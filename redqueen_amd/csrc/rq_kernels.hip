@@ -1126,111 +1126,103 @@ int rq_cu_count()
     }();
     return n;
 }
-template <int SPL, int NK, class COL, int W, bool LOG, bool BITS = false, bool BL = false, bool GS = false,
-          bool MRG = false, bool GT = false>
-static int occ_t(int wpb, size_t lds);
-template <int SPL, int NK, class COL, int W, bool LOG, bool BITS = false, bool BL = false, bool GS = false,
-          bool MRG = false, bool GT = false>
-static hipError_t launch_sweep_t(const SweepArgs& a, hipStream_t s)
+
+// ---- the rq_sweep instance of a SweepInst: the one list of instances ----
+// the fast general sweep: a register window of W = 4 arrivals per source
+constexpr int kGW = 4;
+// the instances on per-sink ranks (no sink bits): one per K variant
+template <int SPL, class COL, int W, bool LOG, bool GS = false, bool MRG = false, bool GT = false>
+static SweepKernel sweep_nk(int nK)
+{
+    switch (nK) {
+    case 1: return rq_sweep<SPL, 1, COL, W, LOG, false, false, GS, MRG, GT>;
+    case 2: return rq_sweep<SPL, 2, COL, W, LOG, false, false, GS, MRG, GT>;
+    case 3: return rq_sweep<SPL, 3, COL, W, LOG, false, false, GS, MRG, GT>;
+    default: return rq_sweep<SPL, 4, COL, W, LOG, false, false, GS, MRG, GT>;
+    }
+}
+// the sequential sweep on its own streams (<= RQ_MAX_STREAMS sources), rings of W = 8; one
+// source per lane when they fit (the per-lane ring state of eight sources costs ~200
+// VGPRs and spills; 16 / 32 per lane spill more -- correctness instances for 513..2048
+// sources, global columns only, 4-deep rings at 32 per lane: LDS)
+template <bool GS>
+static SweepKernel sweep_log(const SweepInst& i)
+{
+    switch (i.spl) {
+    case 1: return i.col16 ? sweep_nk<1, uint16_t, 8, true, GS>(i.nK) : sweep_nk<1, int, 8, true, GS>(i.nK);
+    case 8: return i.col16 ? sweep_nk<8, uint16_t, 8, true, GS>(i.nK) : sweep_nk<8, int, 8, true, GS>(i.nK);
+    case 16: return sweep_nk<16, int, 8, true, GS>(i.nK);
+    default: return sweep_nk<32, int, 4, true, GS>(i.nK);
+    }
+}
+// the fast sweep on merged streams, per-stream tables in LDS
+template <class COL>
+static SweepKernel sweep_mrg(const SweepInst& i)
+{
+    if (i.bl) return rq_sweep<1, 1, COL, kGW, false, false, true, false, true>;
+    if (i.bits) return rq_sweep<1, 1, uint16_t, kGW, false, true, false, false, true>;
+    return sweep_nk<1, COL, kGW, false, false, true>(i.nK);
+}
+// the fast sweep on its own streams, SPL sources per lane
+template <int SPL>
+static SweepKernel sweep_own(const SweepInst& i)
+{
+    if (i.bl) {   // the per-wave sink bits exist for 2+ sources per lane
+        if constexpr (SPL >= 2)
+            return i.col16 ? rq_sweep<SPL, 1, uint16_t, kGW, false, false, true>
+                           : rq_sweep<SPL, 1, int, kGW, false, false, true>;
+        return nullptr;
+    }
+    if (i.bits) return rq_sweep<SPL, 1, uint16_t, kGW, false, true, false>;
+    return i.col16 ? sweep_nk<SPL, uint16_t, kGW, false>(i.nK) : sweep_nk<SPL, int, kGW, false>(i.nK);
+}
+// null: no such instance
+static SweepKernel sweep_kernel(const SweepInst& i)
+{
+    // the sequential sweep on merged streams (> RQ_MAX_STREAMS sources): global columns and
+    // per-stream tables (GT), 4-deep rings the instance never fills
+    if (i.log && i.mrg)
+        return i.gs ? sweep_nk<1, int, 4, true, true, true, true>(i.nK) : sweep_nk<1, int, 4, true, false, true, true>(i.nK);
+    if (i.log) return i.gs ? sweep_log<true>(i) : sweep_log<false>(i);
+    // merged streams with the per-stream tables in global memory (more streams than the
+    // LDS tables take): global columns, no sink bitsets
+    if (i.mrg && i.gt) {
+        if (i.bl) return rq_sweep<1, 1, int, kGW, false, false, true, false, true, true>;
+        if (i.bits) return nullptr;
+        return sweep_nk<1, int, kGW, false, false, true, true>(i.nK);
+    }
+    if (i.mrg) return i.col16 ? sweep_mrg<uint16_t>(i) : sweep_mrg<int>(i);
+    switch (i.spl) {
+    case 1: return sweep_own<1>(i);
+    case 2: return sweep_own<2>(i);
+    case 4: return sweep_own<4>(i);
+    default: return sweep_own<8>(i);
+    }
+}
+
+// ---- the leaf operations on an instance ----
+// blocks of 64*wpb threads per CU a sweep instance reaches with `lds` bytes of dynamic
+// LDS (VGPR, SGPR and LDS limits all applied by the runtime)
+static int occ_t(SweepKernel k, int wpb, size_t lds)
+{
+    return rq_occupancy(k, 64 * wpb, lds);
+}
+static hipError_t launch_sweep_t(SweepKernel k, bool gs, const SweepArgs& a, hipStream_t s)
 {
     unsigned blocks = (unsigned)((a.n_chunk + a.wpb - 1) / a.wpb);
     if (a.wq) {
         // persistent grid: every resident wave slot once, the rest from the queue
-        const int nb_c = occ_t<SPL, NK, COL, W, LOG, BITS, BL, GS, MRG, GT>(a.wpb, a.lds_total);
+        const int nb_c = occ_t(k, a.wpb, a.lds_total);
         const unsigned cap = (unsigned)(nb_c > 0 ? nb_c : 1) * (unsigned)rq_cu_count();
         if (cap < blocks) blocks = cap;
     }
-    if (GS) {   // one global per-sink state slot per wave of the grid
+    if (gs) {   // one global per-sink state slot per wave of the grid
         const unsigned cap = (unsigned)(a.gs_slots / a.wpb);
         if (!a.wq || cap < 1) return hipErrorInvalidValue;
         if (cap < blocks) blocks = cap;
     }
-    hipLaunchKernelGGL((rq_sweep<SPL, NK, COL, W, LOG, BITS, BL, GS, MRG, GT>), dim3(blocks), dim3(64 * a.wpb), a.lds_total,
-                       s, a);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * a.wpb), a.lds_total, s, a);
     return hipGetLastError();
-}
-
-template <int SPL, class COL, int W, bool LOG, bool GS = false>
-static hipError_t launch_sweep_k(const SweepArgs& a, int nK, hipStream_t s)
-{
-    switch (nK) {
-    case 1: return launch_sweep_t<SPL, 1, COL, W, LOG, false, false, GS>(a, s);
-    case 2: return launch_sweep_t<SPL, 2, COL, W, LOG, false, false, GS>(a, s);
-    case 3: return launch_sweep_t<SPL, 3, COL, W, LOG, false, false, GS>(a, s);
-    default: return launch_sweep_t<SPL, 4, COL, W, LOG, false, false, GS>(a, s);
-    }
-}
-
-// the fast general sweep: a register window of W = 4 arrivals per source
-constexpr int kGW = 4;
-template <int SPL>
-static hipError_t launch_sweep_c(const SweepArgs& a, int nK, int col16, int bits, hipStream_t s)
-{
-    if constexpr (SPL >= 2)
-        if (bits == 2)   // K = 1 on per-wave LDS sink bits (> 64 sources)
-            return col16 ? launch_sweep_t<SPL, 1, uint16_t, kGW, false, false, true>(a, s)
-                         : launch_sweep_t<SPL, 1, int, kGW, false, false, true>(a, s);
-    if (bits)   // K = 1 on sink bitsets
-        return launch_sweep_t<SPL, 1, uint16_t, kGW, false, true>(a, s);
-    return col16 ? launch_sweep_k<SPL, uint16_t, kGW, false>(a, nK, s)
-                 : launch_sweep_k<SPL, int, kGW, false>(a, nK, s);
-}
-
-// the sequential sweep on merged streams (> RQ_MAX_STREAMS sources): one instance per K
-// variant and per-sink state placement (GS); per-stream tables in global memory (GT)
-template <bool GS>
-static hipError_t launch_sweep_lm(const SweepArgs& a, int nK, hipStream_t s)
-{
-    switch (nK) {
-    case 1: return launch_sweep_t<1, 1, int, 4, true, false, false, GS, true, true>(a, s);
-    case 2: return launch_sweep_t<1, 2, int, 4, true, false, false, GS, true, true>(a, s);
-    case 3: return launch_sweep_t<1, 3, int, 4, true, false, false, GS, true, true>(a, s);
-    default: return launch_sweep_t<1, 4, int, 4, true, false, false, GS, true, true>(a, s);
-    }
-}
-
-// the fast sweep on merged streams: one instance per (K variant, column type)
-template <int NK, class COL>
-static hipError_t launch_sweep_mk(const SweepArgs& a, hipStream_t s)
-{
-    return launch_sweep_t<1, NK, COL, kGW, false, false, false, false, true>(a, s);
-}
-// the same with the per-stream tables in global memory (GT: more streams than the LDS
-// tables take; global columns, no sink bitsets)
-static hipError_t launch_sweep_mg(const SweepArgs& a, int nK, int bits, hipStream_t s)
-{
-    if (bits == 2) return launch_sweep_t<1, 1, int, kGW, false, false, true, false, true, true>(a, s);
-    if (bits) return hipErrorInvalidValue;
-    switch (nK) {
-    case 1: return launch_sweep_t<1, 1, int, kGW, false, false, false, false, true, true>(a, s);
-    case 2: return launch_sweep_t<1, 2, int, kGW, false, false, false, false, true, true>(a, s);
-    case 3: return launch_sweep_t<1, 3, int, kGW, false, false, false, false, true, true>(a, s);
-    default: return launch_sweep_t<1, 4, int, kGW, false, false, false, false, true, true>(a, s);
-    }
-}
-template <class COL>
-static hipError_t launch_sweep_m(const SweepArgs& a, int nK, int bits, hipStream_t s)
-{
-    if (bits == 2) return launch_sweep_t<1, 1, COL, kGW, false, false, true, false, true>(a, s);
-    if (bits) return launch_sweep_t<1, 1, uint16_t, kGW, false, true, false, false, true>(a, s);
-    switch (nK) {
-    case 1: return launch_sweep_mk<1, COL>(a, s);
-    case 2: return launch_sweep_mk<2, COL>(a, s);
-    case 3: return launch_sweep_mk<3, COL>(a, s);
-    default: return launch_sweep_mk<4, COL>(a, s);
-    }
-}
-template <class COL>
-static int occ_m(int nK, int bits, int wpb, size_t lds)
-{
-    if (bits == 2) return occ_t<1, 1, COL, kGW, false, false, true, false, true>(wpb, lds);
-    if (bits) return occ_t<1, 1, uint16_t, kGW, false, true, false, false, true>(wpb, lds);
-    switch (nK) {
-    case 1: return occ_t<1, 1, COL, kGW, false, false, false, false, true>(wpb, lds);
-    case 2: return occ_t<1, 2, COL, kGW, false, false, false, false, true>(wpb, lds);
-    case 3: return occ_t<1, 3, COL, kGW, false, false, false, false, true>(wpb, lds);
-    default: return occ_t<1, 4, COL, kGW, false, false, false, false, true>(wpb, lds);
-    }
 }
 
 hipError_t rq_launch_gen(const GenArgs& a, hipStream_t s)
@@ -1242,150 +1234,34 @@ hipError_t rq_launch_gen(const GenArgs& a, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t rq_launch_sweep(const SweepArgs& a, int spl, int nK, int col16, int log, int bits, hipStream_t s)
+hipError_t rq_launch_sweep(const SweepArgs& a, const SweepInst& i, hipStream_t s)
 {
     if (a.n_chunk <= 0) return hipSuccess;
-    // event log / max_events / duplicate edges / > 512 sources: the sequential variant,
-    // W = 8; one source per lane when they fit (the per-lane ring state of eight sources
-    // costs ~200 VGPRs and spills; 16 / 32 per lane spill more -- correctness instances
-    // for 513..2048 sources, global columns only)
-    // > 2048 sources: the sequential sweep on merged streams (global columns, 4-deep
-    // rings the instance never fills)
-    if (log && spl <= 0) return log == 2 ? launch_sweep_lm<true>(a, nK, s) : launch_sweep_lm<false>(a, nK, s);
-    if (spl < 0) return launch_sweep_mg(a, nK, bits, s);   // merged streams, global tables
-    if (log == 2)
-        switch (spl) {
-        case 1: return col16 ? launch_sweep_k<1, uint16_t, 8, true, true>(a, nK, s)
-                             : launch_sweep_k<1, int, 8, true, true>(a, nK, s);
-        case 8: return col16 ? launch_sweep_k<8, uint16_t, 8, true, true>(a, nK, s)
-                             : launch_sweep_k<8, int, 8, true, true>(a, nK, s);
-        case 16: return launch_sweep_k<16, int, 8, true, true>(a, nK, s);
-        default: return launch_sweep_k<32, int, 4, true, true>(a, nK, s);   // 4-deep rings: LDS
-        }
-    if (log)
-        switch (spl) {
-        case 1: return col16 ? launch_sweep_k<1, uint16_t, 8, true>(a, nK, s)
-                             : launch_sweep_k<1, int, 8, true>(a, nK, s);
-        case 8: return col16 ? launch_sweep_k<8, uint16_t, 8, true>(a, nK, s)
-                             : launch_sweep_k<8, int, 8, true>(a, nK, s);
-        case 16: return launch_sweep_k<16, int, 8, true>(a, nK, s);
-        default: return launch_sweep_k<32, int, 4, true>(a, nK, s);
-        }
-    if (spl == 0)   // merged streams
-        return col16 ? launch_sweep_m<uint16_t>(a, nK, bits, s) : launch_sweep_m<int>(a, nK, bits, s);
-    switch (spl) {
-    case 1: return launch_sweep_c<1>(a, nK, col16, bits, s);
-    case 2: return launch_sweep_c<2>(a, nK, col16, bits, s);
-    case 4: return launch_sweep_c<4>(a, nK, col16, bits, s);
-    default: return launch_sweep_c<8>(a, nK, col16, bits, s);
-    }
+    const SweepKernel k = sweep_kernel(i);
+    return k ? launch_sweep_t(k, i.log && i.gs, a, s) : hipErrorInvalidValue;
 }
 
-// blocks of 64*wpb threads per CU the chosen sweep instance reaches with `lds`
-// bytes of dynamic LDS (VGPR, SGPR and LDS limits all applied by the runtime)
-template <int SPL, int NK, class COL, int W, bool LOG, bool BITS, bool BL, bool GS, bool MRG, bool GT>
-static int occ_t(int wpb, size_t lds)
+int rq_sweep_blocks_per_cu(const SweepInst& i, int wpb, size_t lds)
 {
-    return rq_occupancy(rq_sweep<SPL, NK, COL, W, LOG, BITS, BL, GS, MRG, GT>, 64 * wpb, lds);
-}
-template <int SPL, class COL, int W, bool LOG, bool GS = false>
-static int occ_k(int nK, int wpb, size_t lds)
-{
-    switch (nK) {
-    case 1: return occ_t<SPL, 1, COL, W, LOG, false, false, GS>(wpb, lds);
-    case 2: return occ_t<SPL, 2, COL, W, LOG, false, false, GS>(wpb, lds);
-    case 3: return occ_t<SPL, 3, COL, W, LOG, false, false, GS>(wpb, lds);
-    default: return occ_t<SPL, 4, COL, W, LOG, false, false, GS>(wpb, lds);
-    }
-}
-template <int SPL>
-static int occ_c(int nK, int col16, int W, int bits, int wpb, size_t lds)
-{
-    (void)W;
-    if constexpr (SPL >= 2)
-        if (bits == 2)
-            return col16 ? occ_t<SPL, 1, uint16_t, kGW, false, false, true>(wpb, lds)
-                         : occ_t<SPL, 1, int, kGW, false, false, true>(wpb, lds);
-    if (bits) return occ_t<SPL, 1, uint16_t, kGW, false, true>(wpb, lds);
-    return col16 ? occ_k<SPL, uint16_t, kGW, false>(nK, wpb, lds) : occ_k<SPL, int, kGW, false>(nK, wpb, lds);
-}
-int rq_sweep_blocks_per_cu(int spl, int nK, int col16, int W, int log, int bits, int wpb, size_t lds)
-{
-    if (spl < 0 && !log) {   // merged streams, global tables (launch_sweep_mg)
-        if (bits == 2) return occ_t<1, 1, int, kGW, false, false, true, false, true, true>(wpb, lds);
-        if (bits) return 0;
-        switch (nK) {
-        case 1: return occ_t<1, 1, int, kGW, false, false, false, false, true, true>(wpb, lds);
-        case 2: return occ_t<1, 2, int, kGW, false, false, false, false, true, true>(wpb, lds);
-        case 3: return occ_t<1, 3, int, kGW, false, false, false, false, true, true>(wpb, lds);
-        default: return occ_t<1, 4, int, kGW, false, false, false, false, true, true>(wpb, lds);
-        }
-    }
-    if (log && spl <= 0) {   // the sequential sweep on merged streams (launch_sweep_lm)
-        const bool gs = log == 2;
-        switch (nK) {
-        case 1: return gs ? occ_t<1, 1, int, 4, true, false, false, true, true, true>(wpb, lds)
-                          : occ_t<1, 1, int, 4, true, false, false, false, true, true>(wpb, lds);
-        case 2: return gs ? occ_t<1, 2, int, 4, true, false, false, true, true, true>(wpb, lds)
-                          : occ_t<1, 2, int, 4, true, false, false, false, true, true>(wpb, lds);
-        case 3: return gs ? occ_t<1, 3, int, 4, true, false, false, true, true, true>(wpb, lds)
-                          : occ_t<1, 3, int, 4, true, false, false, false, true, true>(wpb, lds);
-        default: return gs ? occ_t<1, 4, int, 4, true, false, false, true, true, true>(wpb, lds)
-                           : occ_t<1, 4, int, 4, true, false, false, false, true, true>(wpb, lds);
-        }
-    }
-    if (log == 2)
-        switch (spl) {
-        case 1: return col16 ? occ_k<1, uint16_t, 8, true, true>(nK, wpb, lds) : occ_k<1, int, 8, true, true>(nK, wpb, lds);
-        case 8: return col16 ? occ_k<8, uint16_t, 8, true, true>(nK, wpb, lds) : occ_k<8, int, 8, true, true>(nK, wpb, lds);
-        case 16: return occ_k<16, int, 8, true, true>(nK, wpb, lds);
-        default: return occ_k<32, int, 4, true, true>(nK, wpb, lds);
-        }
-    if (log)
-        switch (spl) {
-        case 1: return col16 ? occ_k<1, uint16_t, 8, true>(nK, wpb, lds) : occ_k<1, int, 8, true>(nK, wpb, lds);
-        case 8: return col16 ? occ_k<8, uint16_t, 8, true>(nK, wpb, lds) : occ_k<8, int, 8, true>(nK, wpb, lds);
-        case 16: return occ_k<16, int, 8, true>(nK, wpb, lds);
-        default: return occ_k<32, int, 4, true>(nK, wpb, lds);
-        }
-    if (spl == 0) return col16 ? occ_m<uint16_t>(nK, bits, wpb, lds) : occ_m<int>(nK, bits, wpb, lds);
-    switch (spl) {
-    case 1: return occ_c<1>(nK, col16, W, bits, wpb, lds);
-    case 2: return occ_c<2>(nK, col16, W, bits, wpb, lds);
-    case 4: return occ_c<4>(nK, col16, W, bits, wpb, lds);
-    default: return occ_c<8>(nK, col16, W, bits, wpb, lds);
-    }
+    const SweepKernel k = sweep_kernel(i);
+    return k ? occ_t(k, wpb, lds) : 0;
 }
 
-template <int NK, int WPE>
-static unsigned scan_blocks(const ScanArgs& a, size_t lds)
-{
-    unsigned blocks = (unsigned)((a.n_chunk + 3) / 4);
-    if (a.wq) {   // persistent grid: every resident block once
-        const int nb = rq_occupancy(rq_scan<NK, WPE>, 256, lds);
-        const unsigned cap = (unsigned)(nb > 0 ? nb : 1) * (unsigned)rq_cu_count();
-        if (cap < blocks) blocks = cap;
-    }
-    return blocks;
-}
 template <int NK>
 static hipError_t launch_scan_t(const ScanArgs& a, hipStream_t s)
 {
     const size_t lds = 4 * npsum_lds_doubles<NK + 2>() * sizeof(double);
-    // waves per SIMD the build targets (VGPR budget): A/B knob RQ_SCAN_WPE.  2 (a whole
-    // leaf per trip, 176 VGPRs at K = 1) measured 0.296 ms on the C3 step's scan against
-    // 0.313 / 0.332 / 0.645 / 0.805 ms at 3 / 4 / 6 / 8 (same box, profiles/r03_scan_ab.txt)
-    static const int wpe = getenv("RQ_SCAN_WPE") ? atoi(getenv("RQ_SCAN_WPE")) : 2;
-    if (wpe >= 8)
-        hipLaunchKernelGGL((rq_scan<NK, 8>), dim3(scan_blocks<NK, 8>(a, lds)), dim3(256), lds, s, a);
-    else if (wpe >= 6)
-        hipLaunchKernelGGL((rq_scan<NK, 6>), dim3(scan_blocks<NK, 6>(a, lds)), dim3(256), lds, s, a);
-    else if (wpe >= 4)
-        hipLaunchKernelGGL((rq_scan<NK, 4>), dim3(scan_blocks<NK, 4>(a, lds)), dim3(256), lds, s, a);
-    else if (wpe == 3)
-        hipLaunchKernelGGL((rq_scan<NK, 3>), dim3(scan_blocks<NK, 3>(a, lds)), dim3(256), lds, s, a);
-    else
-        hipLaunchKernelGGL((rq_scan<NK, 2>), dim3(scan_blocks<NK, 2>(a, lds)), dim3(256), lds, s, a);
+    // the 2 waves per SIMD build (VGPR budget: a whole leaf per trip, 176 VGPRs at K = 1)
+    // measured 0.296 ms on the C3 step's scan against 0.313 / 0.332 / 0.645 / 0.805 ms at
+    // 3 / 4 / 6 / 8 (same box, profiles/r03_scan_ab.txt)
+    constexpr auto k = rq_scan<NK, 2>;
+    unsigned blocks = (unsigned)((a.n_chunk + 3) / 4);
+    if (a.wq) {   // persistent grid: every resident block once
+        const int nb = rq_occupancy(k, 256, lds);
+        const unsigned cap = (unsigned)(nb > 0 ? nb : 1) * (unsigned)rq_cu_count();
+        if (cap < blocks) blocks = cap;
+    }
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(256), lds, s, a);
     return hipGetLastError();
 }
 

@@ -531,86 +531,77 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RQ_FWM_WPE
 // ============================================================================
 // launch wrappers
 // ============================================================================
-// fused windowed sweep: (W, H) in {(16, 8), (8, 4)}; OptPWSignificance (PW) instances
-// exist for uint16 columns and W = 16 only (make_plan keeps other PW runs off this path)
-template <int NK, class COL, int W, bool BITS, bool PW = false, bool MRG = false>
-static int occ_fw_t(int wpb, size_t lds);
-template <int NK, class COL, int W, bool BITS, bool PW = false, bool MRG = false>
-static hipError_t launch_fw_t(const SweepArgs& a, hipStream_t s)
+// ---- the fused instance of a SweepInst: the one list of instances ----
+// generated arrivals: rings of W, a register window of H, (W, H) in {(32, 8), (16, 8), (8, 4)}
+template <class COL, int W, bool PW = false>
+static SweepKernel fw_nk(int nK)
+{
+    constexpr int H = W > 16 ? 8 : W / 2;
+    switch (nK) {
+    case 1: return rq_sweep_fw<1, COL, W, H, false, PW>;
+    case 2: return rq_sweep_fw<2, COL, W, H, false, PW>;
+    case 3: return rq_sweep_fw<3, COL, W, H, false, PW>;
+    default: return rq_sweep_fw<4, COL, W, H, false, PW>;
+    }
+}
+template <class COL>
+static SweepKernel fwm_nk(int nK)
+{
+    switch (nK) {
+    case 1: return rq_sweep_fwm<1, COL, false>;
+    case 2: return rq_sweep_fwm<2, COL, false>;
+    case 3: return rq_sweep_fwm<3, COL, false>;
+    default: return rq_sweep_fwm<4, COL, false>;
+    }
+}
+// null: no such instance
+static SweepKernel fw_kernel(const SweepInst& i)
+{
+    if (i.mrg) {   // merged streams (RedQueen / Poisson / replayed controllers)
+        if (i.pw) return nullptr;
+        if (i.bits) return rq_sweep_fwm<1, uint16_t, true>;
+        return i.col16 ? fwm_nk<uint16_t>(i.nK) : fwm_nk<int>(i.nK);
+    }
+    // OptPWSignificance (PW) instances exist for uint16 columns and W = 16 only (make_plan
+    // keeps other PW runs off this path)
+    if (i.pw) {
+        if (!i.col16 || i.W != 16) return nullptr;
+        return i.bits ? rq_sweep_fw<1, uint16_t, 16, 8, true, true> : fw_nk<uint16_t, 16, true>(i.nK);
+    }
+    if (i.bits)   // 32-deep rings: this K = 1 bitset instance only
+        return i.W == 32 ? rq_sweep_fw<1, uint16_t, 32, 8, true>
+             : i.W == 16 ? rq_sweep_fw<1, uint16_t, 16, 8, true> : rq_sweep_fw<1, uint16_t, 8, 4, true>;
+    if (i.W == 16) return i.col16 ? fw_nk<uint16_t, 16>(i.nK) : fw_nk<int, 16>(i.nK);
+    return i.col16 ? fw_nk<uint16_t, 8>(i.nK) : fw_nk<int, 8>(i.nK);
+}
+
+// ---- the leaf operations on an instance ----
+static int occ_fw_t(SweepKernel k, int wpb, size_t lds)
+{
+    return rq_occupancy(k, 64 * wpb, lds);
+}
+static hipError_t launch_fw_t(SweepKernel k, const SweepArgs& a, hipStream_t s)
 {
     unsigned blocks = (unsigned)((a.n_chunk + a.wpb - 1) / a.wpb);
     if (a.wq) {
         // persistent grid: every resident wave slot once, the rest from the queue
-        const int nb = occ_fw_t<NK, COL, W, BITS, PW, MRG>(a.wpb, a.lds_total);
+        const int nb = occ_fw_t(k, a.wpb, a.lds_total);
         const unsigned cap = (unsigned)(nb > 0 ? nb : 1) * (unsigned)rq_cu_count();
         if (cap < blocks) blocks = cap;
     }
-    if constexpr (MRG)
-        hipLaunchKernelGGL((rq_sweep_fwm<NK, COL, BITS>), dim3(blocks), dim3(64 * a.wpb), a.lds_total, s, a);
-    else
-        hipLaunchKernelGGL((rq_sweep_fw<NK, COL, W, (W > 16 ? 8 : W / 2), BITS, PW, MRG>), dim3(blocks), dim3(64 * a.wpb),
-                           a.lds_total, s, a);
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * a.wpb), a.lds_total, s, a);
     return hipGetLastError();
 }
-template <class COL, int W, bool PW = false, bool MRG = false>
-static hipError_t launch_fw_k(const SweepArgs& a, int nK, hipStream_t s)
-{
-    switch (nK) {
-    case 1: return launch_fw_t<1, COL, W, false, PW, MRG>(a, s);
-    case 2: return launch_fw_t<2, COL, W, false, PW, MRG>(a, s);
-    case 3: return launch_fw_t<3, COL, W, false, PW, MRG>(a, s);
-    default: return launch_fw_t<4, COL, W, false, PW, MRG>(a, s);
-    }
-}
-hipError_t rq_launch_sweep_fw(const SweepArgs& a, int nK, int col16, int W, int bits, hipStream_t s)
+
+hipError_t rq_launch_sweep_fw(const SweepArgs& a, const SweepInst& i, hipStream_t s)
 {
     if (a.n_chunk <= 0) return hipSuccess;
-    if (W == 0) {   // merged streams (RedQueen / Poisson / replayed controllers)
-        if (a.pw_c) return hipErrorInvalidValue;
-        if (bits) return launch_fw_t<1, uint16_t, 16, true, false, true>(a, s);
-        return col16 ? launch_fw_k<uint16_t, 16, false, true>(a, nK, s) : launch_fw_k<int, 16, false, true>(a, nK, s);
-    }
-    if (a.pw_c) {
-        if (!col16 || W != 16) return hipErrorInvalidValue;
-        return bits ? launch_fw_t<1, uint16_t, 16, true, true>(a, s) : launch_fw_k<uint16_t, 16, true>(a, nK, s);
-    }
-    if (bits)
-        return W == 32 ? launch_fw_t<1, uint16_t, 32, true>(a, s)
-             : W == 16 ? launch_fw_t<1, uint16_t, 16, true>(a, s) : launch_fw_t<1, uint16_t, 8, true>(a, s);
-    if (W == 16) return col16 ? launch_fw_k<uint16_t, 16>(a, nK, s) : launch_fw_k<int, 16>(a, nK, s);
-    return col16 ? launch_fw_k<uint16_t, 8>(a, nK, s) : launch_fw_k<int, 8>(a, nK, s);
+    const SweepKernel k = fw_kernel(i);
+    return k ? launch_fw_t(k, a, s) : hipErrorInvalidValue;
 }
-template <int NK, class COL, int W, bool BITS, bool PW, bool MRG>
-static int occ_fw_t(int wpb, size_t lds)
+
+int rq_fw_blocks_per_cu(const SweepInst& i, int wpb, size_t lds)
 {
-    if constexpr (MRG) return rq_occupancy(rq_sweep_fwm<NK, COL, BITS>, 64 * wpb, lds);
-    else return rq_occupancy(rq_sweep_fw<NK, COL, W, (W > 16 ? 8 : W / 2), BITS, PW, MRG>, 64 * wpb, lds);
-}
-template <class COL, int W, bool PW = false, bool MRG = false>
-static int occ_fw_k(int nK, int wpb, size_t lds)
-{
-    switch (nK) {
-    case 1: return occ_fw_t<1, COL, W, false, PW, MRG>(wpb, lds);
-    case 2: return occ_fw_t<2, COL, W, false, PW, MRG>(wpb, lds);
-    case 3: return occ_fw_t<3, COL, W, false, PW, MRG>(wpb, lds);
-    default: return occ_fw_t<4, COL, W, false, PW, MRG>(wpb, lds);
-    }
-}
-// W = 0: the merged-stream instances
-int rq_fw_blocks_per_cu(int nK, int col16, int W, int bits, int wpb, size_t lds, int pw)
-{
-    if (W == 0) {
-        if (pw) return -1;
-        if (bits) return occ_fw_t<1, uint16_t, 16, true, false, true>(wpb, lds);
-        return col16 ? occ_fw_k<uint16_t, 16, false, true>(nK, wpb, lds) : occ_fw_k<int, 16, false, true>(nK, wpb, lds);
-    }
-    if (pw) {
-        if (!col16 || W != 16) return -1;
-        return bits ? occ_fw_t<1, uint16_t, 16, true, true>(wpb, lds) : occ_fw_k<uint16_t, 16, true>(nK, wpb, lds);
-    }
-    if (bits)
-        return W == 32 ? occ_fw_t<1, uint16_t, 32, true>(wpb, lds)
-             : W == 16 ? occ_fw_t<1, uint16_t, 16, true>(wpb, lds) : occ_fw_t<1, uint16_t, 8, true>(wpb, lds);
-    if (W == 16) return col16 ? occ_fw_k<uint16_t, 16>(nK, wpb, lds) : occ_fw_k<int, 16>(nK, wpb, lds);
-    return col16 ? occ_fw_k<uint16_t, 8>(nK, wpb, lds) : occ_fw_k<int, 8>(nK, wpb, lds);
+    const SweepKernel k = fw_kernel(i);
+    return k ? occ_fw_t(k, wpb, lds) : -1;
 }

@@ -12,7 +12,10 @@ GPU, bit for bit against the engine-semantics oracle (oracle/rq_oracle.c):
 * the repeat-stream skip of the per-wave sink-bit sweep (a stream's second event
   before the next reset walks no sinks): on and off, bit for bit;
 * 50k sinks (per-wave sink bits for K = 1, int16 ranks for K > 1, and the
-  sequential sweep with its per-sink state in global memory).
+  sequential sweep with its per-sink state in global memory), and the same world resized
+  to launch the sweep instances no other test reaches (int columns past 65535 sinks; 2 / 4
+  / 8 sources per lane on the windowed sweep; the sequential sweep's per-sink state in
+  global memory at 8 / 16 / 32 per lane and on merged streams).
 
 A duplicated CONTROLLED edge with a RedQueen controller is refused (RQ_EINVAL /
 ValueError): the reference's sqrt_s_by_q (one entry per edge) no longer matches
@@ -284,17 +287,76 @@ def _wide(n_sinks=50000, n_src=40, deg=60, T=4.0):
                 edge_list=edges)
 
 
+_SEQ = dict(sweep_mode=2, event_log=True)
+_WIN = dict(sweep_mode=6)
+
+
 @pytest.mark.parametrize("Ks,kw,variant", [
-    ((1,), {}, 3),                                  # K = 1: per-wave LDS sink bits
+    ((1,), {}, 3),                                 # K = 1: per-wave LDS sink bits
     ((1, 2), {}, 0),                                # int16 ranks, one wave per block (fused or not)
     ((1, 2), dict(sweep_mode=2, event_log=True), 4),   # sequential, per-sink state in HBM
+] + [
+    # Sweep instances no other test launches, one row each.  kw["graph"] resizes the world
+    # (more than 65535 sinks: int columns read from global memory; 100 / 200 / 400 sources:
+    # 2 / 4 / 8 per lane on the windowed sweep, sweep_mode 6; 600 / 1100 / 2100: the
+    # sequential sweep at 16 / 32 per lane and on merged streams) and kw["plan"] is the part
+    # of the plan that names the instance: variant, sources per lane, ring depth, column
+    # placement.
+    (Ks, dict(kw, graph=gk, plan=dict(variant=v, sources_per_lane=spl, ring_depth=W, columns_in_lds=col)), v % 10)
+    for gk, Ks, kw, v, spl, W, col in [
+        # sequential, per-sink state in HBM: the other K counts, int columns, 8 / 16 / 32 per lane
+        ({}, (1,), _SEQ, 4, 1, 8, 1),
+        ({}, (1, 2, 5), _SEQ, 4, 1, 8, 1),
+        ({}, (1, 2, 5, 10), _SEQ, 4, 1, 8, 1),
+        (dict(n_sinks=70000), (1, 2), _SEQ, 4, 1, 8, 0),
+        (dict(n_src=100), (1, 2), _SEQ, 4, 8, 8, 1),
+        (dict(n_src=400, n_sinks=70000, deg=20), (3,), _SEQ, 4, 8, 8, 0),
+        (dict(n_src=600, deg=10), (1, 2, 5), _SEQ, 4, 16, 8, 0),
+        (dict(n_src=1100, deg=10), (1, 2, 5, 10), _SEQ, 4, 32, 4, 0),
+        # sequential on merged streams (> 2048 sources): per-sink state in HBM / in LDS
+        (dict(n_src=2100, deg=5), (1,), _SEQ, 4, 0, 4, 0),
+        (dict(n_src=2100, deg=5, n_sinks=1000), (1, 2, 5), _SEQ, 1, 0, 4, 0),
+        # sequential, per-sink state in LDS, 8 per lane, int columns
+        (dict(n_src=400, n_sinks=1000, deg=20), (1, 2, 5), _SEQ, 1, 8, 8, 0),
+        # fused on merged streams / generating, general on merged streams: int columns
+        (dict(n_sinks=70000), (1, 2), {}, 20, 0, 16, 0),
+        (dict(n_sinks=70000), (3,), {}, 20, 0, 16, 0),
+        (dict(n_sinks=70000), (1, 2, 5), dict(sweep_mode=7), 10, 1, 16, 0),
+        (dict(n_sinks=70000), (3,), dict(sweep_mode=7), 10, 1, 16, 0),
+        # generating, rings of 8: 79001 int16 ranks per wave leave no room for rings of 16
+        (dict(n_sinks=79000), (1, 2), dict(sweep_mode=7), 10, 1, 8, 0),
+        (dict(n_sinks=70000), (1, 2, 5), dict(sweep_mode=4), 0, 0, 4, 0),
+        # K = 1 on merged streams: per-wave sink bits, int columns
+        (dict(n_sinks=70000), (1,), {}, 3, 0, 4, 0),
+        # windowed sweep: 1 / 2 / 4 / 8 sources per lane on ranks, uint16 and int columns
+        (dict(n_sinks=70000), (1, 2, 5, 10), _WIN, 0, 1, 4, 0),
+        (dict(n_src=100), (1, 2), _WIN, 0, 2, 4, 1),
+        (dict(n_src=100, n_sinks=70000), (1, 2, 5, 10), _WIN, 0, 2, 4, 0),
+        (dict(n_src=200), (3,), _WIN, 0, 4, 4, 1),
+        (dict(n_src=200, n_sinks=70000), (1, 2), _WIN, 0, 4, 4, 0),
+        (dict(n_src=400, n_sinks=1000, deg=20), (1, 2, 5, 10), _WIN, 0, 8, 4, 1),
+        (dict(n_src=400, n_sinks=70000, deg=20), (1, 2, 5), _WIN, 0, 8, 4, 0),
+        # windowed sweep, K = 1: per-wave sink bits at 2 / 4 / 8 per lane, sink bitsets at 8
+        ({}, (1,), _WIN, 3, 2, 4, 1),
+        (dict(n_src=200), (1,), _WIN, 3, 4, 4, 1),
+        (dict(n_src=400, deg=20), (1,), _WIN, 3, 8, 4, 1),
+        (dict(n_src=100, n_sinks=70000), (1,), _WIN, 3, 2, 4, 0),
+        (dict(n_src=200, n_sinks=70000), (1,), _WIN, 3, 4, 4, 0),
+        (dict(n_src=400, n_sinks=70000, deg=20), (1,), _WIN, 3, 8, 4, 0),
+        (dict(n_src=400, n_sinks=1000, deg=20), (1,), _WIN, 2, 8, 4, 1),
+    ]
 ])
 def test_50k_sinks(Ks, kw, variant):
+    """The wide world (50k sinks; the later rows resize it to reach one sweep instance
+    each): the plan names the expected instance and the run == the engine oracle."""
     torch, engine, graphs, O = _ctx()
-    so = _wide()
+    kw = dict(kw)
+    so = _wide(**kw.pop("graph", {}))
+    want = kw.pop("plan", {})
     g = _graph(engine, so)
     plan = g.run("opt", q=so["q"], s=so["s"], n_rep=6, Ks=Ks, plan_only=True, **kw)
     assert plan["variant"] % 10 == variant, plan
+    assert {k: plan[k] for k in want} == want, plan
     res = g.run("opt", q=so["q"], s=so["s"], n_rep=6, ctrl_seed=70, world_seed=70, randomize=True,
                 Ks=Ks, **kw)
     assert int(res.status.max().item()) == 0
