@@ -266,6 +266,9 @@ struct Plan {
     // the fused sweep's phases B / C on merged streams (rq_gen_streams + rq_merge_streams
     // instead of in-kernel generation; sweep_mode 7: the in-kernel generating sweep)
     bool fwm = false;
+    // fwm with the RedQueen controller: its Exp(1) draws by call pairs (SweepInst.pair;
+    // RQ_CTRL_DRAWS=0 keeps a Philox call per draw)
+    bool pair = false;
     // general sweep LDS layout
     int gwpb = 4, gwin = 16, gcol_lds = 1, gcol16 = 0;
     size_t g_col = 0, g_ptr = 0, g_odf = 0, g_cbf = 0, g_wave = 0, g_wave_stride = 0, g_rank_off = 0,
@@ -369,6 +372,7 @@ SweepInst sweep_inst(const Plan& p, int ctrl_kind, bool fused, int W, bool col16
     i.W = W;
     i.gt = gt;
     i.pw = ctrl_kind == RQ_SRC_OPTPW;   // exactly the runs rq_run_batch gives SweepArgs.pw_c
+    i.pair = fused && i.mrg && p.pair;
     return i;
 }
 // the instance a finished plan runs
@@ -636,6 +640,8 @@ void plan_fused_lds(const rq_graph* g, const rq_batch_desc* b, Plan* p)
             b->sweep_mode != 6;
     p->fwm = p->fw && !pw && b->sweep_mode != 7;
     if (const char* e = getenv("RQ_FWM")) p->fwm = p->fwm && atoi(e) != 0;   // A/B only
+    p->pair = p->fwm && b->ctrl_kind == RQ_SRC_OPT;
+    if (const char* e = getenv("RQ_CTRL_DRAWS")) p->pair = p->pair && atoi(e) != 0;   // A/B and tests
     if (p->fw) {
         int best = -1;
         const int c16 = p->bits ? 1 : (g->n_sinks <= 65535 ? 1 : 0);
@@ -685,6 +691,7 @@ void plan_fused_lds(const rq_graph* g, const rq_batch_desc* b, Plan* p)
         if (best < 0) p->fw = false;
     }
     if (!p->fw) p->fwm = false;
+    if (!p->fwm) p->pair = false;
     if (p->fw) p->mrg = p->fwm;   // the merge kernel feeds the fused sweep too
 }
 

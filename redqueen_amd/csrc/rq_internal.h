@@ -223,6 +223,8 @@ struct SweepInst {
                   //   instances fix theirs: a window of 4; log: rings of 8, 4 at 32 per lane)
     bool gt;      // mrg, general: the per-stream tables in global memory
     bool pw;      // fused: the OptPWSignificance controller
+    bool pair;    // fused, mrg: the RedQueen controller's draws by call pairs (one Philox call per
+                  //   lane every other tile, both of its draws used), else a call per draw
 };
 using SweepKernel = void (*)(SweepArgs);
 

@@ -473,13 +473,15 @@ __device__ __forceinline__ double optpw_sample(double tt, const double* row, dou
     return RQ_INF;
 }
 
-template <bool PW>
+//  XIN: lane q's draw arrives as xd (the caller drew it: the same bits as the Philox call
+//  below), so the tile runs no generator.
+template <bool PW, bool XIN = false>
 __device__ __forceinline__ void controller_tile(int n, bool act, double tt, int tj, const double* invc,
                                                 const int* cbf, uint32_t oseed, uint64_t& ndraw,
                                                 double& opt_next, uint64_t& ownm, double& ot,
                                                 const double* pwc = nullptr,
                                                 const double* pwmax = nullptr, int S = 0,
-                                                double T = 0.0)
+                                                double T = 0.0, double xd = 0.0)
 {
     const int lane = lane_id();
     double c = RQ_INF;
@@ -488,12 +490,14 @@ __device__ __forceinline__ void controller_tile(int n, bool act, double tt, int 
         c = optpw_sample(tt, pwc + (size_t)tj * S, pwmax[tj], S, T, ndraw + (uint64_t)lane, oseed);
         cb = cbf[tj] != 0;
     } else if (act) {
-        const uint64_t d = ndraw + (uint64_t)lane;   // draw d: Philox call d>>1, half d&1
-        const uint64_t call = d >> 1;
-        uint32_t w4[4] = {(uint32_t)call, (uint32_t)(call >> 32), 0u, 0u};
-        philox4x32_10(w4, oseed, kind_salt(RQ_SRC_OPT, true));
-        const double x = rq_std_exponential((d & 1) ? rq_uniform53(w4[2], w4[3])
-                                                    : rq_uniform53(w4[0], w4[1]));
+        double x = xd;
+        if constexpr (!XIN) {
+            const uint64_t d = ndraw + (uint64_t)lane;   // draw d: Philox call d>>1, half d&1
+            const uint64_t call = d >> 1;
+            uint32_t w4[4] = {(uint32_t)call, (uint32_t)(call >> 32), 0u, 0u};
+            philox4x32_10(w4, oseed, kind_salt(RQ_SRC_OPT, true));
+            x = rq_std_exponential((d & 1) ? rq_uniform53(w4[2], w4[3]) : rq_uniform53(w4[0], w4[1]));
+        }
         const double ic = invc[tj];
         const double e = ic > 0.0 ? x * ic : RQ_INF;
         c = tt + e;

@@ -37,7 +37,12 @@ using namespace rq;
 // MRG: the arrivals come pre-generated (rq_gen_streams) and merged into the replica's
 // (t, stream) sequence (rq_merge_streams): a tile is its next 64 entries, loaded one tile
 // ahead, and phase A (refill passes, window cut, rank sort) disappears
-template <int NK, class COL, int W, int H, bool BITS, bool PW, bool MRG>
+// PAIR (MRG, RedQueen controller): the controller's draws by call pairs.  Draw d is half
+// d & 1 of Philox call d >> 1, and a tile starts at a multiple of 64 draws, so lanes 2k and
+// 2k + 1 of controller_tile each run call k and keep one half.  Here every other tile
+// each lane runs ONE call and both of its logarithms, and the 128 draws of that tile and
+// the next reach their lanes by cross-lane reads: half the Philox calls, the same bits.
+template <int NK, class COL, int W, int H, bool BITS, bool PW, bool MRG, bool PAIR = false>
 __device__ __forceinline__ void sweep_fw_body(SweepArgs a)
 {
     static_assert((W & (W - 1)) == 0 && H <= W, "ring");
@@ -139,6 +144,7 @@ __device__ __forceinline__ void sweep_fw_body(SweepArgs a)
     const int64_t k = a.seed_mod > 0 ? i % a.seed_mod : i;
     const uint32_t oseed = a.ctrl_seed ? a.ctrl_seed[i] : a.ctrl_seed0 + (uint32_t)k;
     uint64_t ndraw = 0;   // wall events seen so far = the controller's draw index
+    double px0 = 0.0, px1 = 0.0;   // PAIR: both draws of this lane's call of the current tile pair
     auto colat = [&](int e) -> int { return col_lds ? (int)col_l[e] : col_g[e]; };
     const int fol0 = cptr[a.ctrl_idx];
     auto folat = [&](int f) -> int { return colat(fol0 + f); };
@@ -179,7 +185,7 @@ __device__ __forceinline__ void sweep_fw_body(SweepArgs a)
     for (;;) {
         int n = 0;
         bool act, fin;
-        double tt;
+        double tt, tx = 0.0;   // tx: the entry's controller draw (PAIR)
         int tj;
         if constexpr (MRG) {
             if (mpos >= mlen) break;   // every arrival played
@@ -194,6 +200,22 @@ __device__ __forceinline__ void sweep_fw_body(SweepArgs a)
             nxt_t = RQ_INF;
             nxt_j = 0;
             if (mpos + lane < mlen) mload(mpos + lane, nxt_t, nxt_j);
+            if constexpr (PAIR) {
+                // ndraw = 64 x the tile's index (every tile before the last holds 64 entries,
+                // a max_events cut ends the replica): an even tile draws calls ndraw / 2 + lane,
+                // lane l of it takes draw ndraw + l from lane l / 2, of the next from 32 + l / 2
+                const uint32_t tile = (uint32_t)(ndraw >> 6);
+                if ((tile & 1u) == 0u) {
+                    const uint64_t call = (ndraw >> 1) + (uint64_t)lane;
+                    uint32_t w4[4] = {(uint32_t)call, (uint32_t)(call >> 32), 0u, 0u};
+                    philox4x32_10(w4, oseed, kind_salt(RQ_SRC_OPT, true));
+                    px0 = rq_std_exponential(rq_uniform53(w4[0], w4[1]));
+                    px1 = rq_std_exponential(rq_uniform53(w4[2], w4[3]));
+                }
+                const int srcl = (int)((tile & 1u) << 5) + (lane >> 1);
+                const double y0 = __shfl(px0, srcl, 64), y1 = __shfl(px1, srcl, 64);
+                tx = (lane & 1) ? y1 : y0;
+            }
             RQ_CLK(2);
         } else {
         // ---- A1: opportunistic passes while >= thr rings are below W; if some unfinished
@@ -303,8 +325,8 @@ __device__ __forceinline__ void sweep_fw_body(SweepArgs a)
         // ---- B: RedQueen controller over the tile ----
         uint64_t ownm = 0;
         double ot = RQ_INF;
-        if (opt && a.dbg != 3) controller_tile<PW>(n, act, tt, tj, invc, cbf, oseed, ndraw, opt_next, ownm, ot, pwc, pwm, a.n_seg,
-                            a.period);
+        if (opt && a.dbg != 3) controller_tile<PW, PAIR>(n, act, tt, tj, invc, cbf, oseed, ndraw, opt_next, ownm, ot, pwc, pwm, a.n_seg,
+                            a.period, tx);
 
         RQ_CLK(3);   // B controller
         // max_events: the tile keeps the events numbered below it, the replica ends here
@@ -522,10 +544,10 @@ __global__ __launch_bounds__(1024) void rq_sweep_fw(SweepArgs a)
 #ifndef RQ_FWM_WPE
 #define RQ_FWM_WPE 4
 #endif
-template <int NK, class COL, bool BITS>
+template <int NK, class COL, bool BITS, bool PAIR = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RQ_FWM_WPE))) void rq_sweep_fwm(SweepArgs a)
 {
-    sweep_fw_body<NK, COL, 16, 8, BITS, false, true>(a);
+    sweep_fw_body<NK, COL, 16, 8, BITS, false, true, PAIR>(a);
 }
 
 // ============================================================================
@@ -544,14 +566,14 @@ static SweepKernel fw_nk(int nK)
     default: return rq_sweep_fw<4, COL, W, H, false, PW>;
     }
 }
-template <class COL>
+template <class COL, bool PAIR>
 static SweepKernel fwm_nk(int nK)
 {
     switch (nK) {
-    case 1: return rq_sweep_fwm<1, COL, false>;
-    case 2: return rq_sweep_fwm<2, COL, false>;
-    case 3: return rq_sweep_fwm<3, COL, false>;
-    default: return rq_sweep_fwm<4, COL, false>;
+    case 1: return rq_sweep_fwm<1, COL, false, PAIR>;
+    case 2: return rq_sweep_fwm<2, COL, false, PAIR>;
+    case 3: return rq_sweep_fwm<3, COL, false, PAIR>;
+    default: return rq_sweep_fwm<4, COL, false, PAIR>;
     }
 }
 // null: no such instance
@@ -559,9 +581,14 @@ static SweepKernel fw_kernel(const SweepInst& i)
 {
     if (i.mrg) {   // merged streams (RedQueen / Poisson / replayed controllers)
         if (i.pw) return nullptr;
+        if (i.pair) {   // the RedQueen controller's draws by call pairs
+            if (i.bits) return rq_sweep_fwm<1, uint16_t, true, true>;
+            return i.col16 ? fwm_nk<uint16_t, true>(i.nK) : fwm_nk<int, true>(i.nK);
+        }
         if (i.bits) return rq_sweep_fwm<1, uint16_t, true>;
-        return i.col16 ? fwm_nk<uint16_t>(i.nK) : fwm_nk<int>(i.nK);
+        return i.col16 ? fwm_nk<uint16_t, false>(i.nK) : fwm_nk<int, false>(i.nK);
     }
+    if (i.pair) return nullptr;   // call pairs: the merged instances only
     // OptPWSignificance (PW) instances exist for uint16 columns and W = 16 only (make_plan
     // keeps other PW runs off this path)
     if (i.pw) {
@@ -596,6 +623,7 @@ static hipError_t launch_fw_t(SweepKernel k, const SweepArgs& a, hipStream_t s)
 hipError_t rq_launch_sweep_fw(const SweepArgs& a, const SweepInst& i, hipStream_t s)
 {
     if (a.n_chunk <= 0) return hipSuccess;
+    if (i.pair && a.ctrl_kind != RQ_SRC_OPT) return hipErrorInvalidValue;
     const SweepKernel k = fw_kernel(i);
     return k ? launch_fw_t(k, a, s) : hipErrorInvalidValue;
 }
