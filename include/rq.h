@@ -274,6 +274,11 @@ int rq_event_capacity(rq_graph_t g, const rq_batch_desc* b, int64_t* cap);
  * 0 without a device), [5] sink columns in LDS (1) or global (0), [6] dynamic LDS
  * bytes per block, [7] replicas per chunk */
 int rq_plan_info(rq_graph_t g, const rq_batch_desc* b, int64_t* info);
+/* the first n entries of the same list, which continues: [8] the sweep integrates each
+ * replica's rows itself and the chunk launches no scan kernel (1; the merged fused sweep
+ * without event log or max_events, RQ_SWEEP_SCAN=0 in the environment turns it off) or the
+ * scan kernel runs after the sweep (0).  Entries past the last defined one are not written. */
+int rq_plan_info_n(rq_graph_t g, const rq_batch_desc* b, int64_t* info, int n);
 
 int rq_run_batch(rq_graph_t g, const rq_batch_desc* b, const rq_outputs* out,
                  void* workspace, size_t workspace_bytes, void* hip_stream);

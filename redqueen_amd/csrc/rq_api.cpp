@@ -269,6 +269,9 @@ struct Plan {
     // fwm with the RedQueen controller: its Exp(1) draws by call pairs (SweepInst.pair;
     // RQ_CTRL_DRAWS=0 keeps a Philox call per draw)
     bool pair = false;
+    // fwm without event log or max_events: each wave integrates the rows of the replica it
+    // swept (SweepInst.scan), the chunk launches no rq_scan; RQ_SWEEP_SCAN=0 keeps the kernel
+    bool scan = false;
     // general sweep LDS layout
     int gwpb = 4, gwin = 16, gcol_lds = 1, gcol16 = 0;
     size_t g_col = 0, g_ptr = 0, g_odf = 0, g_cbf = 0, g_wave = 0, g_wave_stride = 0, g_rank_off = 0,
@@ -373,6 +376,7 @@ SweepInst sweep_inst(const Plan& p, int ctrl_kind, bool fused, int W, bool col16
     i.gt = gt;
     i.pw = ctrl_kind == RQ_SRC_OPTPW;   // exactly the runs rq_run_batch gives SweepArgs.pw_c
     i.pair = fused && i.mrg && p.pair;
+    i.scan = fused && i.mrg && p.scan;
     return i;
 }
 // the instance a finished plan runs
@@ -642,6 +646,8 @@ void plan_fused_lds(const rq_graph* g, const rq_batch_desc* b, Plan* p)
     if (const char* e = getenv("RQ_FWM")) p->fwm = p->fwm && atoi(e) != 0;   // A/B only
     p->pair = p->fwm && b->ctrl_kind == RQ_SRC_OPT;
     if (const char* e = getenv("RQ_CTRL_DRAWS")) p->pair = p->pair && atoi(e) != 0;   // A/B and tests
+    p->scan = p->fwm && !(b->flags & RQ_RUN_EVENT_LOG) && b->max_events < 0;
+    if (const char* e = getenv("RQ_SWEEP_SCAN")) p->scan = p->scan && atoi(e) != 0;   // A/B and tests
     if (p->fw) {
         int best = -1;
         const int c16 = p->bits ? 1 : (g->n_sinks <= 65535 ? 1 : 0);
@@ -669,7 +675,9 @@ void plan_fused_lds(const rq_graph* g, const rq_batch_desc* b, Plan* p)
             const size_t w_off = align_up(r_off + (p->bits ? 8 * (size_t)((g->nw + 1) & ~1) : 2 * (size_t)p->n_sinks_pad), 16);
             // merged streams: no arrival rings
             const size_t s_off = align_up(w_off + (p->fwm ? 0 : 8 * (size_t)g->n_str * (W + 1)), 16);
-            const size_t stride = align_up(s_off + 64 * 12, 16);
+            size_t stride = align_up(s_off + 64 * 12, 16);
+            // the sweep's own scan aliases the wave's area (dead after the tile loop)
+            if (p->scan) stride = std::max(stride, align_up(RQ_FWS_LDS_BYTES(p->nK), 16));
             for (int wpb : {16, 12, 10, 8, 6, 5, 4, 3, 2, 1}) {
                 const size_t tot = sh + wpb * stride;
                 if (tot > kLdsMax) continue;
@@ -691,7 +699,7 @@ void plan_fused_lds(const rq_graph* g, const rq_batch_desc* b, Plan* p)
         if (best < 0) p->fw = false;
     }
     if (!p->fw) p->fwm = false;
-    if (!p->fwm) p->pair = false;
+    if (!p->fwm) p->pair = p->scan = false;
     if (p->fw) p->mrg = p->fwm;   // the merge kernel feeds the fused sweep too
 }
 
@@ -1148,7 +1156,13 @@ int rq_workspace_size(rq_graph_t g, const rq_batch_desc* b, size_t* bytes)
 
 int rq_plan_info(rq_graph_t g, const rq_batch_desc* b, int64_t* info)
 {
-    if (!info) return RQ_EINVAL;
+    return rq_plan_info_n(g, b, info, 8);
+}
+
+int rq_plan_info_n(rq_graph_t g, const rq_batch_desc* b, int64_t* out, int n)
+{
+    if (!out || n < 0) return RQ_EINVAL;
+    int64_t info[9];
     Plan p;
     const int rc = make_plan(g, b, &p, ws_budget(b, 0.0));
     if (rc) return rc;
@@ -1160,6 +1174,8 @@ int rq_plan_info(rq_graph_t g, const rq_batch_desc* b, int64_t* info)
     info[5] = p.gcol_lds;
     info[6] = (int64_t)p.g_total;
     info[7] = p.chunk;
+    info[8] = p.scan ? 1 : 0;
+    std::copy(info, info + std::min(n, 9), out);
     return RQ_OK;
 }
 
@@ -1514,6 +1530,7 @@ int rq_run_batch(rq_graph_t g, const rq_batch_desc* b, const rq_outputs* out, vo
             sa.clk = phase_clk();
 #endif
             sa.lds_total = p.g_total;
+            sa.metrics = out->metrics;
             sa.lds_stage_off = p.g_stage_off;
             sa.gen = ga;
             // fused sweep: waves past their first replica take the next one from a queue,
@@ -1530,6 +1547,7 @@ int rq_run_batch(rq_graph_t g, const rq_batch_desc* b, const rq_outputs* out, vo
             if (e != hipSuccess) return RQ_EHIP;
         }
 
+        if (p.scan) continue;   // the sweep's waves integrated their own rows
         ScanArgs sc{};
         sc.n_chunk = C;
         sc.chunk0 = c0;

@@ -413,12 +413,15 @@ __device__ __forceinline__ uint64_t order_key(double t)
 // VAL(k, v) fills v[0..NV) with element k of each sequence.
 // lds: >= rq_npsum_lds_doubles<NV>() doubles, private to this wave.
 // ---------------------------------------------------------------------------
-template <int NV>
+// NL: the capacity in leaves (and in nodes of a level).  A block of <= 8192 elements has
+// <= 65 leaves (below), so any NL >= 66 holds every plan; 128 is the historical layout.
+template <int NV, int NL = 128>
 __host__ __device__ constexpr int npsum_lds_doubles()
 {
-    // leaf values [NV][128] + leaf (off,len) [128][2 ints = 1 double] + the tree's levels
-    // [8][128] uint16 + their node counts [8] ints
-    return NV * 128 + 128 + 256 + 4;
+    // leaf values [NV][NL] + leaf (off,len) [NL][2 ints = 1 double] + the tree's levels
+    // [8][NL] uint16 + their node counts [8] ints
+    static_assert(NL >= 66 && NL % 2 == 0, "a block's plan has up to 65 leaves");
+    return NV * NL + NL + 2 * NL + 4;
 }
 
 // numpy's pairwise tree over m <= 8192 elements (pairwise_sum: a node of len > 128
@@ -430,9 +433,10 @@ __host__ __device__ constexpr int npsum_lds_doubles()
 // unchanged, so the last level is the leaves left to right.  Leaves hold >= 64 elements
 // unless m <= 128, hence <= 65 leaves and depth <= 7 (8192 = 1024 units, 6 halvings to
 // 16 units, one more for the remainder).
-// leaf[2L] / leaf[2L+1]: leaf L's offset / length; lev[d * 128 + j]: node j of level d's
-// first child index at level d + 1 | (split << 8); cnt[d]: nodes at level d; tmp: 128
+// leaf[2L] / leaf[2L+1]: leaf L's offset / length; lev[d * NL + j]: node j of level d's
+// first child index at level d + 1 | (split << 8); cnt[d]: nodes at level d; tmp: NL
 // ints of scratch.  Returns the leaf count; depth = the last level's index.
+template <int NL = 128>
 __device__ __forceinline__ int npsum_plan(int m, int* leaf, uint16_t* lev, int* cnt, int* tmp, int& depth)
 {
     const int lane = lane_id();
@@ -467,12 +471,12 @@ __device__ __forceinline__ int npsum_plan(int m, int* leaf, uint16_t* lev, int* 
         const int cA = lane + popc(bA & lt);
         const int cB = lane + 64 + pA + popc(bB & lt);
         if (vA) {
-            lev[d * 128 + lane] = (uint16_t)(cA | (sA ? 256 : 0));
+            lev[d * NL + lane] = (uint16_t)(cA | (sA ? 256 : 0));
             tmp[cA] = sA ? (kA >> 1) : kA;
             if (sA) tmp[cA + 1] = (kA + 1) >> 1;
         }
         if (vB) {
-            lev[d * 128 + lane + 64] = (uint16_t)(cB | (sB ? 256 : 0));
+            lev[d * NL + lane + 64] = (uint16_t)(cB | (sB ? 256 : 0));
             tmp[cB] = sB ? (kB >> 1) : kB;
             if (sB) tmp[cB + 1] = (kB + 1) >> 1;
         }
@@ -486,11 +490,11 @@ __device__ __forceinline__ int npsum_plan(int m, int* leaf, uint16_t* lev, int* 
     }
 }
 
-// fold the leaf values leafv[s * 128 + L] up the planned tree in place, level by level
+// fold the leaf values leafv[s * NL + L] up the planned tree in place, level by level
 // (node j's children sit at indices >= j, and every read of a level precedes its
 // writes): a split node is left + right in numpy's order, a pass-through node keeps its
 // child's value bit for bit (-0.0 included).  The root's values end in cv (every lane).
-template <int NV>
+template <int NV, int NL = 128>
 __device__ __forceinline__ void npsum_fold(int depth, const uint16_t* lev, const int* cnt, double* leafv,
                                            double cv[NV])
 {
@@ -499,26 +503,26 @@ __device__ __forceinline__ void npsum_fold(int depth, const uint16_t* lev, const
         const int n = cnt[d];
         double vA[NV], vB[NV];
         const bool okA = lane < n, okB = lane + 64 < n;
-        const int eA = okA ? lev[d * 128 + lane] : 0;
-        const int eB = okB ? lev[d * 128 + lane + 64] : 0;
+        const int eA = okA ? lev[d * NL + lane] : 0;
+        const int eB = okB ? lev[d * NL + lane + 64] : 0;
         const int cA = eA & 255, cB = eB & 255;
 #pragma unroll
         for (int s = 0; s < NV; ++s) {
-            vA[s] = leafv[s * 128 + cA];
-            vB[s] = leafv[s * 128 + cB];
-            if (eA & 256) vA[s] = vA[s] + leafv[s * 128 + cA + 1];
-            if (eB & 256) vB[s] = vB[s] + leafv[s * 128 + cB + 1];
+            vA[s] = leafv[s * NL + cA];
+            vB[s] = leafv[s * NL + cB];
+            if (eA & 256) vA[s] = vA[s] + leafv[s * NL + cA + 1];
+            if (eB & 256) vB[s] = vB[s] + leafv[s * NL + cB + 1];
         }
         wave_lds_sync();
 #pragma unroll
         for (int s = 0; s < NV; ++s) {
-            if (okA) leafv[s * 128 + lane] = vA[s];
-            if (okB) leafv[s * 128 + lane + 64] = vB[s];
+            if (okA) leafv[s * NL + lane] = vA[s];
+            if (okB) leafv[s * NL + lane + 64] = vB[s];
         }
         wave_lds_sync();
     }
 #pragma unroll
-    for (int s = 0; s < NV; ++s) cv[s] = leafv[s * 128];
+    for (int s = 0; s < NV; ++s) cv[s] = leafv[s * NL];
     wave_lds_sync();   // before the next chunk's plan reuses leafv as scratch
 }
 
@@ -624,16 +628,16 @@ __device__ __forceinline__ double dpp_shr7_f64(double x)
     return rq_bits_dbl(((uint64_t)hi << 32) | lo);
 }
 
-template <int NV, bool TNEXT, class Row, int TU = 8, class LD, class TLD, class VF>
+template <int NV, bool TNEXT, class Row, int TU = 8, int NL = 128, class LD, class TLD, class VF>
 __device__ void wave_npsum_rows(int64_t n, double end, LD&& ld, TLD&& tld, VF&& vf, double* lds,
                                 double out[NV])
 {
     const int lane = lane_id();
     const int grp = lane >> 3, jj = lane & 7;
     double* leafv = lds;
-    int* leaf = reinterpret_cast<int*>(lds + NV * 128);
-    uint16_t* levt = reinterpret_cast<uint16_t*>(lds + NV * 128 + 128);   // [8][128]
-    int* lcnt = reinterpret_cast<int*>(lds + NV * 128 + 128 + 256);         // [8]
+    int* leaf = reinterpret_cast<int*>(lds + NV * NL);
+    uint16_t* levt = reinterpret_cast<uint16_t*>(lds + NV * NL + NL);   // [8][NL]
+    int* lcnt = reinterpret_cast<int*>(lds + NV * NL + 3 * NL);         // [8]
     double res[NV];
 #pragma unroll
     for (int s = 0; s < NV; ++s) res[s] = 0.0;
@@ -641,7 +645,7 @@ __device__ void wave_npsum_rows(int64_t n, double end, LD&& ld, TLD&& tld, VF&& 
     for (int64_t c0 = 0; c0 < n; c0 += 8192) {
         const int m = (int)((n - c0) < 8192 ? (n - c0) : 8192);
         int depth = 0;
-        const int nleaf = npsum_plan(m, leaf, levt, lcnt, reinterpret_cast<int*>(leafv), depth);
+        const int nleaf = npsum_plan<NL>(m, leaf, levt, lcnt, reinterpret_cast<int*>(leafv), depth);
         for (int L0 = 0; L0 < nleaf; L0 += 8) {
             const int L = L0 + grp;
             const bool act = L < nleaf;
@@ -704,14 +708,14 @@ __device__ void wave_npsum_rows(int64_t n, double end, LD&& ld, TLD&& tld, VF&& 
                     for (int s = 0; s < NV; ++s) r[s] += v[s];
                 }
 #pragma unroll
-                for (int s = 0; s < NV; ++s) leafv[s * 128 + L] = r[s];
+                for (int s = 0; s < NV; ++s) leafv[s * NL + L] = r[s];
             }
         }
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         double cv[NV];
-        npsum_fold<NV>(depth, levt, lcnt, leafv, cv);
+        npsum_fold<NV, NL>(depth, levt, lcnt, leafv, cv);
 #pragma unroll
         for (int s = 0; s < NV; ++s) res[s] = res[s] + cv[s];
         __builtin_amdgcn_wave_barrier();

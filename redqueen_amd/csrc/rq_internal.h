@@ -112,7 +112,8 @@ struct SweepArgs {
     int fw_thr;              // fused sweep: opportunistic refill passes while >= fw_thr rings are below W
     int fw_hfill;            // fused sweep: a forced refill run ends once every ring shows >= fw_hfill
     int* wq;                 // fused sweep: replica work queue (zeroed per launch; null = one replica per wave)
-    int col_in_lds, win;     // general sweep: CSR copied to LDS; arrival-ring depth
+    double* metrics;         // SweepInst.scan: [R][nK + 2], written by the sweep's own scan (else unused)
+    int col_in_lds, win;    // general sweep: CSR copied to LDS; arrival-ring depth
     size_t lds_col, lds_ptr, lds_odf, lds_cbf, lds_wave, lds_wave_stride, lds_rank_off, lds_win_off, lds_x_off, lds_mask,
         lds_total, lds_stage_off;
     GenArgs gen;             // fused sweep: arrival generation parameters
@@ -225,7 +226,14 @@ struct SweepInst {
     bool pw;      // fused: the OptPWSignificance controller
     bool pair;    // fused, mrg: the RedQueen controller's draws by call pairs (one Philox call per
                   //   lane every other tile, both of its draws used), else a call per draw
+    bool scan;    // fused, mrg: the wave that swept a replica integrates its rows itself (rq_scan's
+                  //   sums, written to SweepArgs.metrics; no rq_scan launch for the chunk)
 };
+// SweepInst.scan: the per-wave LDS of the sweep's scan, aliased on the wave's sweep area
+// (dead after the tile loop, initialised again at the top of each replica); the layout of
+// rq::npsum_lds_doubles<nK + 2, RQ_FWS_NL>() -- 66 leaf slots, a block of 8192 rows has <= 65
+#define RQ_FWS_NL 66
+#define RQ_FWS_LDS_BYTES(nK) ((size_t)8 * (((nK) + 2 + 3) * RQ_FWS_NL + 4))
 using SweepKernel = void (*)(SweepArgs);
 
 hipError_t rq_launch_gen(const GenArgs& a, hipStream_t s);

@@ -29,6 +29,7 @@
 #include "rq_internal.h"
 #include "rq_sweep_core.h"
 #include "rq_gen.h"
+#include "rq_scan_rows.h"
 #include <type_traits>
 #include <algorithm>
 #include <cstdlib>
@@ -1073,32 +1074,10 @@ __global__ __launch_bounds__(256, WPE) void rq_scan(ScanArgs a)
         if (n <= 0) {
             if (lane_id() < NV) out[lane_id()] = __builtin_nan("");
         } else {
-            struct Row {
-                double t, s;
-                uint32_t v, c[NK];
-            };
-            auto ld = [&](uint32_t kk) {
-                Row r;
-                r.t = Rt[kk];
-                r.s = Rs[kk];
-                r.v = Rv[kk];
-#pragma unroll
-                for (int q = 0; q < NK; ++q) r.c[q] = Rc[kk * NK + q];
-                return r;
-            };
-            auto tld = [&](uint32_t kk) { return Rt[kk]; };
-            auto vf = [&](const Row& r, double t1, double* v) {
-                const double dt = t1 - r.t;
-                const double m = r.s / (double)r.v;
-#pragma unroll
-                for (int q = 0; q < NK; ++q) v[q] = ((double)r.c[q] / S) * dt;
-                v[NK] = m * dt;
-                v[NK + 1] = (m * m) * dt;
-            };
             double res[NV];
             // fewer waves / SIMD: the registers for a whole leaf (<= 16 rows per lane) in
             // one trip (2), or for the 10-11 rows of C3's 80-88-row leaves (3)
-            wave_npsum_rows<NV, true, Row, (WPE <= 2 ? 16 : WPE == 3 ? 12 : 8)>(n, end, ld, tld, vf, lds, res);
+            scan_rows<NK, (WPE <= 2 ? 16 : WPE == 3 ? 12 : 8)>(n, S, end, Rt, Rs, Rv, Rc, lds, res);
             if (lane_id() == 0) {
 #pragma unroll
                 for (int s = 0; s < NV; ++s) out[s] = res[s];

@@ -14,6 +14,7 @@
 #include "rq_internal.h"
 #include "rq_sweep_core.h"
 #include "rq_gen.h"
+#include "rq_scan_rows.h"
 #include <type_traits>
 #include <cstdlib>
 
@@ -42,10 +43,48 @@ using namespace rq;
 // 2k + 1 of controller_tile each run call k and keep one half.  Here every other tile
 // each lane runs ONE call and both of its logarithms, and the 128 draws of that tile and
 // the next reach their lanes by cross-lane reads: half the Philox calls, the same bits.
-template <int NK, class COL, int W, int H, bool BITS, bool PW, bool MRG, bool PAIR = false>
+// SCAN (MRG): the wave integrates the rows of the replica it has just swept (scan_rows:
+// rq_scan's sums, bit for bit) before it takes the next replica, so the chunk needs no
+// rq_scan launch.  Producer and consumer of the rows are the same wave: its stores drained
+// and a workgroup-scope fence order them, nothing crosses a CU.  The scan's LDS aliases the
+// wave's sweep area, which is dead by then and initialised again at the top of a replica.
+//
+// fws_tu: rows per lane and trip of that scan (TU of wave_npsum_rows; rq_scan runs 16 at
+// 176 VGPRs).  The kernel stays at 128 VGPRs and 4 waves per SIMD, and the scan's registers
+// come on top of what lives across the replica loop.  At 8 the tile loop of every instance
+// spills; at 4 the one-K instances' (sink bits and columns) are free of scratch, at 2 the
+// two-K instances' too.  The three- and four-K instances stand at 128 VGPRs without the
+// scan and keep a few scratch accesses per tile at any TU, also with the scan as a call
+// (DESIGN §15).
+constexpr int fws_tu(int nk) { return nk == 1 ? 4 : 2; }
+template <int NK>
+__device__ __forceinline__ void fw_scan_rows(int64_t n, double S, double end, const double* Rt, const double* Rs,
+                                             const uint32_t* Rv, const uint32_t* Rc, double* lds, double* out)
+{
+    constexpr int NV = NK + 2;
+    static_assert(RQ_FWS_LDS_BYTES(NK) == 8 * (size_t)npsum_lds_doubles<NV, RQ_FWS_NL>(), "the planner's size");
+    const int lane = lane_id();
+    if (n == 0) {
+        if (lane < NV) out[lane] = __builtin_nan("");
+        return;
+    }
+    // every row was stored by this wave: drain its stores, then order them before its
+    // loads at workgroup scope (same wave, same CU: no L2 write-back)
+    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    double res[NV];
+    scan_rows<NK, fws_tu(NK), RQ_FWS_NL>(n, S, end, Rt, Rs, Rv, Rc, lds, res);
+    if (lane == 0) {
+#pragma unroll
+        for (int s = 0; s < NV; ++s) out[s] = res[s];
+    }
+}
+template <int NK, class COL, int W, int H, bool BITS, bool PW, bool MRG, bool PAIR = false, bool SCAN = false>
 __device__ __forceinline__ void sweep_fw_body(SweepArgs a)
 {
     static_assert((W & (W - 1)) == 0 && H <= W, "ring");
+    static_assert(!SCAN || MRG, "the sweep's own scan: merged instances only");
     extern __shared__ double lds_g[];
     char* base = reinterpret_cast<char*>(lds_g);
     const int lane = lane_id();
@@ -527,6 +566,10 @@ __device__ __forceinline__ void sweep_fw_body(SweepArgs a)
         if (rs.nrow == 0) status |= RQ_ST_EMPTY;
         if (status) atomicOr(&a.status[o], status);
     }
+    if constexpr (SCAN)
+        fw_scan_rows<NK>(rs.nrow, (double)ag.nvalid, a.end, a.rows_t + rbase, a.rows_sum + rbase,
+                         a.rows_valid + rbase, a.rows_cnt + rbase * NK, reinterpret_cast<double*>(wb),
+                         a.metrics + o * (NK + 2));
     if (!a.wq) break;
     int nx = 0;
     if (lane == 0) nx = atomicAdd(a.wq, 1);
@@ -544,10 +587,10 @@ __global__ __launch_bounds__(1024) void rq_sweep_fw(SweepArgs a)
 #ifndef RQ_FWM_WPE
 #define RQ_FWM_WPE 4
 #endif
-template <int NK, class COL, bool BITS, bool PAIR = false>
+template <int NK, class COL, bool BITS, bool PAIR = false, bool SCAN = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RQ_FWM_WPE))) void rq_sweep_fwm(SweepArgs a)
 {
-    sweep_fw_body<NK, COL, 16, 8, BITS, false, true, PAIR>(a);
+    sweep_fw_body<NK, COL, 16, 8, BITS, false, true, PAIR, SCAN>(a);
 }
 
 // ============================================================================
@@ -566,29 +609,33 @@ static SweepKernel fw_nk(int nK)
     default: return rq_sweep_fw<4, COL, W, H, false, PW>;
     }
 }
-template <class COL, bool PAIR>
+template <class COL, bool PAIR, bool SCAN>
 static SweepKernel fwm_nk(int nK)
 {
     switch (nK) {
-    case 1: return rq_sweep_fwm<1, COL, false, PAIR>;
-    case 2: return rq_sweep_fwm<2, COL, false, PAIR>;
-    case 3: return rq_sweep_fwm<3, COL, false, PAIR>;
-    default: return rq_sweep_fwm<4, COL, false, PAIR>;
+    case 1: return rq_sweep_fwm<1, COL, false, PAIR, SCAN>;
+    case 2: return rq_sweep_fwm<2, COL, false, PAIR, SCAN>;
+    case 3: return rq_sweep_fwm<3, COL, false, PAIR, SCAN>;
+    default: return rq_sweep_fwm<4, COL, false, PAIR, SCAN>;
     }
+}
+// the merged instances: (call pairs) x (the sweep's own scan)
+template <bool PAIR, bool SCAN>
+static SweepKernel fwm_kernel(const SweepInst& i)
+{
+    if (i.bits) return rq_sweep_fwm<1, uint16_t, true, PAIR, SCAN>;
+    return i.col16 ? fwm_nk<uint16_t, PAIR, SCAN>(i.nK) : fwm_nk<int, PAIR, SCAN>(i.nK);
 }
 // null: no such instance
 static SweepKernel fw_kernel(const SweepInst& i)
 {
     if (i.mrg) {   // merged streams (RedQueen / Poisson / replayed controllers)
         if (i.pw) return nullptr;
-        if (i.pair) {   // the RedQueen controller's draws by call pairs
-            if (i.bits) return rq_sweep_fwm<1, uint16_t, true, true>;
-            return i.col16 ? fwm_nk<uint16_t, true>(i.nK) : fwm_nk<int, true>(i.nK);
-        }
-        if (i.bits) return rq_sweep_fwm<1, uint16_t, true>;
-        return i.col16 ? fwm_nk<uint16_t, false>(i.nK) : fwm_nk<int, false>(i.nK);
+        if (i.pair)   // the RedQueen controller's draws by call pairs
+            return i.scan ? fwm_kernel<true, true>(i) : fwm_kernel<true, false>(i);
+        return i.scan ? fwm_kernel<false, true>(i) : fwm_kernel<false, false>(i);
     }
-    if (i.pair) return nullptr;   // call pairs: the merged instances only
+    if (i.pair || i.scan) return nullptr;   // call pairs, the sweep's own scan: the merged instances only
     // OptPWSignificance (PW) instances exist for uint16 columns and W = 16 only (make_plan
     // keeps other PW runs off this path)
     if (i.pw) {
@@ -624,6 +671,9 @@ hipError_t rq_launch_sweep_fw(const SweepArgs& a, const SweepInst& i, hipStream_
 {
     if (a.n_chunk <= 0) return hipSuccess;
     if (i.pair && a.ctrl_kind != RQ_SRC_OPT) return hipErrorInvalidValue;
+    // the sweep's own scan: its LDS inside the wave's area, no event log or max_events cut
+    if (i.scan && (!a.metrics || a.ev_t || a.max_events >= 0 || a.lds_wave_stride < RQ_FWS_LDS_BYTES(i.nK)))
+        return hipErrorInvalidValue;
     const SweepKernel k = fw_kernel(i);
     return k ? launch_fw_t(k, a, s) : hipErrorInvalidValue;
 }
