@@ -24,6 +24,12 @@ installed and there is no network) and records, as plain data:
   sweepq.npz       utils.sweep_q (sequential) on std_poisson(1, 100): q_init, the
                    returned q and calc_q_capacity_iter per (q, seed);
                    rank_of_src_in_df tables and u_int_opt values
+  analysis_edges.npz (--analysis-edges) utils.oracle_ranking on synthetic single-follower
+                   walls with n on rq_oracle_dp's wavefront / block widths (63 ... 1025;
+                   repeated times; a q = 0, all-zero-gap wall of lhs == rhs ties) and
+                   utils.rank_of_src_in_df on frames of 1 / 63 / 64 / 65 / 129 sinks with
+                   100+ row t groups, double and triple (t, sink) rows, a late first row
+                   and an absent src_id; one frame with a single unique t
   scale_logs.npz   (--scale-logs) whole reference runs at the headline scale: 8 C3 runs
                    and 2 runs of graphs.c5_mid (500 bursty Hawkes sources, T = 1000):
                    event logs, df shape + column crc32s, utils.py's metrics on the df
@@ -456,6 +462,147 @@ def gen_sweepq():
     rec["rt_k5_uint"] = np.asarray([U.u_int_opt(df3, sim_opts=so3)])
     rec["rt_k5_tab"] = U.rank_of_src_in_df(df3, 1).values
     np.savez_compressed(os.path.join(HERE, "sweepq.npz"), **rec)
+
+
+EDGE_WALL_N = [63, 64, 65, 127, 128, 255, 256, 257, 1023, 1024, 1025]
+EDGE_WALL_ZERO_N = [64, 257, 1024]   # a second wall with ~20 % repeated times
+
+
+def edge_rank_frame(rs, S, n_events):
+    """A df for rank_of_src_in_df at rq_rank_table's edges: S sinks, own posts (src 1)
+    first and last, a burst of 100+ rows at one t, double and triple (t, sink) rows,
+    a world / own / world cell (a k/3 mean) and one sink first seen in the last third."""
+    sinks = np.sort(rs.choice(np.arange(10, 5000), S, replace=False)).astype(np.int64)
+    late = int(sinks[rs.randint(S)]) if S > 1 else None
+    early = [int(x) for x in sinks if x != late]
+    rows = []
+    t = 0.25
+
+    def post(e, src, ss):
+        for y in ss:
+            rows.append((100 + e, 0.0, int(src), t, int(y)))
+
+    burst_at, frac_at, late_at = n_events // 3, n_events // 2, (2 * n_events) // 3 + 2
+    e = 0
+    for step in range(n_events):
+        pool = early if (late is None or step < late_at) else early + [late]
+        if step > 0 and rs.rand() > 0.3:
+            t = t + float(rs.exponential(0.5))
+        own = step == 0 or step == n_events - 1 or rs.rand() < 0.2
+        k = rs.randint(1, min(len(pool), 6) + 1)
+        ss = [int(x) for x in rs.choice(pool, k, replace=False)]
+        u = rs.rand()
+        if u < 0.10:
+            ss += [ss[0], ss[0]]
+        elif u < 0.25:
+            ss.append(ss[0])
+        if late is not None and step == late_at:
+            ss.append(late)
+        post(e, 1 if own else rs.randint(2, 6), ss)
+        e += 1
+        if step == burst_at:       # 100+ rows at this t: spans rq_rank_table's 64-row batches
+            n0 = len(rows)
+            while len(rows) - n0 < 110:
+                k = rs.randint(1, min(len(pool), 6) + 1)
+                post(e, 1 if rs.rand() < 0.2 else rs.randint(2, 6),
+                     [int(x) for x in rs.choice(pool, k, replace=False)])
+                e += 1
+        if step == frac_at:        # world, own, world on one sink at a fresh t: (r + 2) / 3
+            t = t + 0.125
+            for src in (2, 1, 3):
+                post(e, src, [pool[0]])
+                e += 1
+            t = t + 0.125
+    return pd.DataFrame.from_records(rows, columns=["event_id", "time_delta", "src_id", "t",
+                                                    "sink_id"])
+
+
+def gen_analysis_edges():
+    """utils.oracle_ranking (utils.py:181-245) on synthetic single-follower walls whose n
+    sits on rq_oracle_dp's wavefront / block widths, and utils.rank_of_src_in_df
+    (:38-56) on frames at rq_rank_table's 64-column / 64-row boundaries."""
+    rec, walls = {}, []
+    rs = np.random.RandomState(20240607)
+    base = SimOpts.std_poisson(world_seed=1, world_rate=100.0)
+
+    def wall(key, times, end, qs, s):
+        n = len(times)
+        df = pd.DataFrame({"event_id": np.arange(100, 100 + n), "time_delta": np.zeros(n),
+                           "src_id": np.full(n, 2), "t": times, "sink_id": np.full(n, 1001)})
+        rec[key + "_t"] = np.asarray(times, dtype=np.float64)
+        rec[key + "_end"] = np.asarray([end])
+        rec[key + "_q"] = np.asarray(qs, dtype=np.float64)
+        rec[key + "_s"] = np.asarray([s])
+        for i, q in enumerate(qs):
+            odf, cost = U.oracle_ranking(df=df, sim_opts=base.update({"q": q, "s": s,
+                                                                      "end_time": end}))
+            assert np.array_equal(odf.t.values[1:], times)
+            rec["%s_%d_cost" % (key, i)] = np.asarray([cost])
+            rec["%s_%d_events" % (key, i)] = odf.events.values.astype(np.int64)
+            rec["%s_%d_ranks" % (key, i)] = odf.ranks.values.astype(np.int64)
+        walls.append(key)
+
+    for i, n in enumerate(EDGE_WALL_N):
+        for zp in ([0.0, 0.2] if n in EDGE_WALL_ZERO_N else [0.0]):
+            gaps = rs.exponential(0.01, n)
+            gaps[rs.rand(n) < zp] = 0.0
+            times = np.cumsum(gaps)
+            s = [1.0, 2.5, 0.5][i % 3]
+            # the first q posts every other event or so, the second rarely
+            wall("w%d%s" % (n, "z" if zp else ""), times, float(times[-1]) + 0.5,
+                 [0.01 * (1 + 0.3 * i), 1.0 + i], s)
+            ev = rec["w%d%s_0_events" % (n, "z" if zp else "")]
+            assert 0 < ev.sum() < n
+    # every gap zero and q = 0: lhs == rhs in every cell the walk visits -> no post
+    wall("wtie", np.zeros(65), 0.0, [0.0], 1.0)
+    assert rec["wtie_0_events"].sum() == 0 and rec["wtie_0_ranks"][-1] == 65
+    rec["walls"] = np.asarray(walls)
+
+    frames = []
+    for S, ne in ((1, 60), (63, 110), (64, 110), (65, 110), (129, 100)):
+        key = "rt%d" % S
+        df = edge_rank_frame(rs, S, ne)
+        _df_cols(rec, key, df)
+        for src in (1, -1):
+            tab = U.rank_of_src_in_df(df, src)
+            nof = U.rank_of_src_in_df(df, src, fill=False)
+            rec["%s_%d" % (key, src + 1)] = tab.values
+            rec["%s_%d_nofill" % (key, src + 1)] = nof.values
+            own_nof = nof if src == 1 else own_nof
+        rec[key + "_index"] = tab.index.values
+        rec[key + "_cols"] = tab.columns.values.astype(np.int64)
+        # what the frame must contain
+        cell = df.groupby(["t", "sink_id"]).size()
+        assert df.groupby("t").size().max() >= 100 and (cell == 2).any() and (cell == 3).any()
+        tri = [own_nof.values[own_nof.index.get_loc(tt), own_nof.columns.get_loc(kk)] * 3
+               for (tt, kk), c in cell.items() if c == 3]
+        assert any(abs(x - round(x)) < 1e-9 and round(x) % 3 for x in tri)   # a k/3 cell
+        assert df.src_id.values[0] == 1 and df.src_id.values[-1] == 1 and tab.shape[0] <= 200
+        if S > 1:
+            first = np.argmax(~np.isnan(nof.values), axis=0)
+            assert first.max() >= (2 * tab.shape[0]) // 3
+        frames.append(key)
+    d65 = pd.DataFrame({c: rec["rt65_" + c] for c in ["event_id", "time_delta", "src_id", "t",
+                                                      "sink_id"]})
+    by_eid = U.rank_of_src_in_df(d65, 1, with_time=False)
+    rec["rt65_eid_2"] = by_eid.values
+    rec["rt65_eid_index"] = by_eid.index.values.astype(np.int64)
+    # one unique t
+    n1 = 40
+    d1 = pd.DataFrame({"event_id": np.arange(100, 100 + n1), "time_delta": np.zeros(n1),
+                       "src_id": np.where(rs.rand(n1) < 0.3, 1, 2), "t": np.full(n1, 3.5),
+                       "sink_id": rs.choice([7, 8, 9, 11, 12], n1)})
+    _df_cols(rec, "rt_one", d1)
+    for src in (1, -1):
+        rec["rt_one_%d" % (src + 1)] = U.rank_of_src_in_df(d1, src).values
+        rec["rt_one_%d_nofill" % (src + 1)] = U.rank_of_src_in_df(d1, src, fill=False).values
+    rec["rt_one_index"] = np.asarray([3.5])
+    rec["rt_one_cols"] = np.unique(d1.sink_id.values).astype(np.int64)
+    frames.append("rt_one")
+    rec["frames"] = np.asarray(frames)
+    path = os.path.join(HERE, "analysis_edges.npz")
+    np.savez_compressed(path, **rec)
+    assert os.path.getsize(path) <= 1000000, os.path.getsize(path)
 
 
 def gen_errors():
@@ -1134,13 +1281,19 @@ if __name__ == "__main__":
     ap.add_argument("--c5m-start", type=int, default=0, help="append to dist_c5m.npz from here")
     ap.add_argument("--scale-logs", action="store_true",
                     help="only scale_logs.npz: whole reference runs of C3 and c5_mid")
+    ap.add_argument("--analysis-edges", action="store_true",
+                    help="only analysis_edges.npz: oracle walls and rank tables at kernel edges")
     a = ap.parse_args()
     steps = {"npsum": gen_npsum, "draws": gen_draws, "readme": gen_readme, "kats": gen_kats,
              "adv": gen_adversarial, "graphs": gen_graphs, "frac": gen_frac,
              "oracle": gen_oracle, "sweepq": gen_sweepq, "sig": gen_sig, "realdata": gen_realdata,
              "plugin": gen_plugin, "errors": gen_errors, "dynplugin": gen_dynplugin,
              "gridtie": gen_gridtie}
-    if a.c5m_dist:
+    if a.analysis_edges:
+        gen_analysis_edges()
+        print("done analysis edges", flush=True)
+        a.worlds = True   # nothing else
+    elif a.c5m_dist:
         gen_c5m_dist(a.c5m_dist, a.c5m_start, a.procs)
         print("done c5m dist", flush=True)
         a.worlds = True   # nothing else

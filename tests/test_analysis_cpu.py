@@ -10,6 +10,7 @@ import pandas as pd
 import pytest
 
 from oracle import oracle as O
+from tests import analysis_edges as E
 from redqueen_amd import _lib as L
 from redqueen_amd import utils as U
 from redqueen_amd.opt_model import SimOpts
@@ -72,6 +73,94 @@ def test_rank_table_restatement_matches_reference(golden):
     d5 = df_of(g, "rt_k5")
     tab, _, _ = O.rank_table(d5.t.values, d5.src_id.values, d5.sink_id.values, 1)
     assert np.array_equal(tab, g["rt_k5_tab"], equal_nan=True)
+
+
+def edge_walls(g):
+    """(key, w, q, s, cost, events, ranks) of every wall x q of analysis_edges.npz."""
+    for key in g["walls"]:
+        key = str(key)
+        w = E.wall_w(g[key + "_t"], float(g[key + "_end"][0]))
+        for i, q in enumerate(g[key + "_q"]):
+            k = "%s_%d" % (key, i)
+            yield k, w, float(q), float(g[key + "_s"][0]), g[k + "_cost"][0], g[k + "_events"], \
+                g[k + "_ranks"]
+
+
+def test_oracle_dp_restatement_matches_edge_fixtures(golden):
+    """The C oracle equals the reference on walls of n = 63 ... 1025 (repeated times, the
+    q = 0 all-tie wall): it stands in for the reference at the sizes the reference's
+    pure-Python double loop cannot reach."""
+    n_checked = 0
+    for k, w, q, s, cost, ev, rk in edge_walls(golden("analysis_edges.npz")):
+        c2, e2, r2 = O.oracle_dp(w, q, s)
+        assert c2 == cost and np.array_equal(e2, ev) and np.array_equal(r2, rk), k
+        assert ev[-1] == 0 and rk[0] == 0
+        n_checked += 1
+    assert n_checked == 2 * (11 + 3) + 1
+
+
+def test_rank_table_restatement_matches_edge_fixtures(golden):
+    g = golden("analysis_edges.npz")
+    assert [str(f) for f in g["frames"]] == ["rt1", "rt63", "rt64", "rt65", "rt129", "rt_one"]
+    for key in g["frames"]:
+        key = str(key)
+        df = df_of(g, key)
+        for src in (1, -1):
+            for fill, k in ((True, "%s_%d" % (key, src + 1)), (False, "%s_%d_nofill" % (key, src + 1))):
+                tab, idx, sinks = O.rank_table(df.t.values, df.src_id.values, df.sink_id.values,
+                                               src, fill)
+                assert E.same_bits(tab, g[k]), k
+                assert np.array_equal(idx, g[key + "_index"]), k
+                assert np.array_equal(sinks, g[key + "_cols"]), k
+    d = df_of(g, "rt65")
+    tab, idx, _ = O.rank_table(d.event_id.values.astype(np.float64), d.src_id.values,
+                               d.sink_id.values, 1)
+    assert E.same_bits(tab, g["rt65_eid_2"]) and np.array_equal(idx, g["rt65_eid_index"])
+
+
+def test_u_int_inputs_show_sum_order_and_fma():
+    """What tests/test_gpu_analysis_edges.py relies on: numpy's np.sum is the pairwise
+    sum the oracle restates, a left-to-right sum of the same x differs from it from
+    n_t = 129 on (every case with a follower; without one x is all zeros), and a fused
+    multiply-add in the follower dot changes bits."""
+    for n_t in E.UI_NT:
+        for n_f in E.UI_NF:
+            x = E.u_int_x(*E.u_int_case(n_t, n_f))
+            assert np.sum(x) == O.npsum(x), (n_t, n_f)
+            if n_t >= 129 and n_f >= 1:
+                assert E.seq_sum(x) != np.sum(x), (n_t, n_f)
+            if n_f == 0:
+                assert not x.any()
+    table, index, fcol, wts, end = E.u_int_case(9, 5)
+    u = np.zeros(9)
+    for f in range(5):
+        u = u + table[:, fcol[f]] * wts[f]
+    assert (E.u_rows_fma(table, fcol, wts) != u).any()
+    assert E.fma(1.0 + 2.0 ** -30, 1.0 - 2.0 ** -30, -1.0) == -2.0 ** -60
+
+
+def test_dirty_chains_round_where_the_export_tests_need_it():
+    """The event times of tests/test_gpu_export_edges.py: at every spot the reference's
+    accumulated State.time misses t_k (s + (t_k - s) != t_k), and after a spot the
+    next time_delta differs from t_{k+1} - t_k, so the carried state matters."""
+    for start in (0.0, 20.0):
+        for spots in (E.DIRTY_SPOTS, E.DIRTY_SPOTS_B):
+            t = E.dirty_chain(3000, start, spots)
+            assert t[0] >= start and (np.diff(t) >= 0).all()
+            st, td = E.state_times(t, start)
+            assert np.array_equal(td, O.state_time_deltas(t, start))
+            prev = np.concatenate([[start], st[:-1]])
+            dirty = np.nonzero(prev + (t - prev) != t)[0]
+            assert list(dirty) == sorted(spots)
+            for k in spots:
+                assert 1e3 < t[k] / prev[k] < 1e4
+            after = [k for k in spots if td[k + 1] != t[k + 1] - t[k]]
+            assert len(after) >= 2
+            # a dirty event closes chunk 0 (index 1023) and a plain one opens chunk 1:
+            # its time_delta needs the carried State.time, not t[1023]
+            if 1024 not in spots:
+                assert 1023 in after
+    assert 1023 in E.DIRTY_SPOTS and 1024 in E.DIRTY_SPOTS and 1024 not in E.DIRTY_SPOTS_B
 
 
 def test_sweep_q_control_flow_matches_reference(golden, monkeypatch):
