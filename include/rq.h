@@ -32,6 +32,10 @@
  *   rq_u_int            utils.u_int_opt(df, ...)            utils.py:59-81
  *   rq_log_rows /       State.get_dataframe()               opt_model.py:85-97
  *   rq_log_expand       for every replica of an RQ_RUN_EVENT_LOG batch at once
+ *   rq_log_timeline     utils.rank_of_src_in_df + time_in_top_k / average_rank /
+ *                       int_r_2 split over time bins         utils.py:38-56, :84-121
+ *                       and the posts per (sink, segment) opt_runs.py:69-84 counts,
+ *                       for every replica of an RQ_RUN_EVENT_LOG batch at once
  *
  * Conventions
  *   - every function returns 0 (RQ_OK) or a negative rq_status; no C++
@@ -373,6 +377,55 @@ int rq_log_expand(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const
                   int64_t n_rep, int64_t ev_cap, const int64_t* row_off, int64_t* event_id,
                   double* time_delta, int64_t* src_id, double* t, int64_t* sink_id,
                   void* hip_stream);
+
+/* Time-resolved metrics of a batch's event logs: the integrals rq_outputs.metrics holds
+ * over the whole horizon, split over n_bins time bins [edges[b], edges[b+1]), straight
+ * from the compact log (no dataframe rows are written).  ev_t / ev_src / counts are
+ * rq_run_batch's outputs (RQ_RUN_EVENT_LOG) or any arrays in that layout, ev_cap their row
+ * stride; replica i plays its first min(counts[i][2], ev_cap) events and reads nothing
+ * past them.
+ *   Events play in log order.  An event of stream j at t gives every sink x of j's edges
+ * one row: rank_x = 0 if j is the controlled stream, else rank_x + 1 (1 for a sink without
+ * a row so far) -- rank_of_src_in_df's steps_to, utils.py:43-46.  The pivot row at t is
+ * nvalid (sinks with a row so far), sumR (the sum of their ranks) and c_K (those with
+ * rank <= K-1); it holds until the next event that has an edge, the last one until the
+ * graph's end_time.  With S = the sinks seen by the end of the replica (the df's pivot
+ * columns), the integrands are c_K / S, m = sumR / nvalid and m^2, and
+ *   metrics[i][b][.] = sum over rows of f_row * |[t_row, t_next) n [edges[b], edges[b+1])|
+ * in the field order of rq_outputs.metrics (top_K..., avg_rank, r_2).  Time before the
+ * first row contributes nothing, a bin no row overlaps is exactly 0.0, the bins need not
+ * cover the horizon; over bins that do, the fields sum to rq_outputs.metrics up to
+ * rounding (the order of summation differs: <= (rows + 8) ulp).
+ *   posts[i][b] = events with at least one edge and edges[b] <= t < edges[b+1]: [0] the
+ * controlled stream's, [1] every other stream's (over covering bins they sum to
+ * counts[i][0] and counts[i][1]).  wall_posts[i][x][b] (optional) = rows of sink x from
+ * the other streams under the same bin rule; x indexes the graph's sinks in ascending
+ * sink-id order (the pivot's column order).
+ *   status[i]: 0; RQ_ST_TIE when some sink got two rows at one t (pandas' fractional
+ * pivot mean: not computed, the replica's metrics are NaN; equal times on disjoint sinks
+ * are exact and not flagged); RQ_ST_EMPTY when no event had an edge (metrics NaN).  posts
+ * and wall_posts of a flagged replica are valid, and no replica's output depends on its
+ * neighbours or on the launch: one wavefront plays a replica and writes each of its
+ * output elements once (wall_posts included: no zeroing pass, no atomics).
+ *   edges: device [n_bins + 1], strictly increasing and finite (the caller's contract; a
+ * bin with edges[b+1] <= edges[b] is empty, and nothing is accessed out of bounds
+ * whatever edges holds).  Ks: host, 1 <= nK <= RQ_MAX_K, K >= 1.  Enqueues on hip_stream
+ * only: no allocation, no synchronisation, no workspace.
+ *   RQ_EUNSUPPORTED: a graph with duplicate edges (one sink, several rows per event), or
+ * with more than RQ_TIMELINE_MAX_SINKS sinks (the per-sink state -- 8 bytes, 12 with
+ * wall_posts -- lives in one workgroup's LDS).
+ *   Added without an ABI version change (RQ_ABI_VERSION stays 6: no existing layout or
+ * entry changed); a caller detects the function by its symbol. */
+#define RQ_TIMELINE_MAX_SINKS 12288
+int rq_log_timeline(rq_graph_t g, const double* ev_t, const int32_t* ev_src,
+                    const int64_t* counts, int64_t n_rep, int64_t ev_cap,
+                    const double* edges, int32_t n_bins,      /* device [n_bins + 1] */
+                    const int32_t* Ks, int32_t nK,            /* host, 1 <= nK <= 4, K >= 1 */
+                    double* metrics,      /* device [n_rep][n_bins][nK + 2] */
+                    int64_t* posts,       /* device [n_rep][n_bins][2]: own, other */
+                    int32_t* wall_posts,  /* device [n_rep][n_sinks][n_bins] or NULL */
+                    int32_t* status,      /* device [n_rep] */
+                    void* hip_stream);
 
 /* Per-kernel timing for benchmarks: rq_timing(1) starts recording HIP events
  * around every kernel this library launches (on the caller's stream);

@@ -66,6 +66,7 @@ REPLAY_CHUNKED = 2
 REPLAY_CHUNK_ROWS = 4096   # RC_L: rows per workgroup of the chunked replay
 MAX_K = 4
 MAX_RD = 64
+TIMELINE_MAX_SINKS = 12288   # RQ_TIMELINE_MAX_SINKS
 
 _P = C.c_void_p
 _pd = C.POINTER(C.c_double)
@@ -153,13 +154,16 @@ def lib():
                            C.c_size_t, _P]
     L.rq_log_rows.argtypes = [_P, _P, _P, C.c_int64, C.c_int64, _P, _P]
     L.rq_log_expand.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, _P]
+    L.rq_log_timeline.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int32, _pi32,
+                                  C.c_int32, _P, _P, _P, _P, _P]
     L.rq_timing.argtypes = [C.c_int]
     L.rq_timing_read.argtypes = [_pd, _pi64]
     for fn in ("rq_timing", "rq_timing_read", "rq_graph_build", "rq_graph_free", "rq_graph_info", "rq_graph_source_ids",
                "rq_graph_followers", "rq_workspace_size", "rq_event_capacity", "rq_run_batch",
                "rq_replay_workspace_size", "rq_metrics_replay", "rq_metrics_replay_batch",
                "rq_oracle_workspace_size",
-               "rq_oracle_dp", "rq_rank_table", "rq_u_int", "rq_log_rows", "rq_log_expand"):
+               "rq_oracle_dp", "rq_rank_table", "rq_u_int", "rq_log_rows", "rq_log_expand",
+               "rq_log_timeline"):
         getattr(L, fn).restype = C.c_int
     if L.rq_abi_version() != ABI_VERSION:
         raise ImportError("librq.so ABI version mismatch")
@@ -205,4 +209,4 @@ EXPORTED = ["rq_abi_version", "rq_strerror", "rq_graph_build", "rq_graph_free", 
             "rq_graph_source_ids", "rq_graph_followers", "rq_workspace_size",
             "rq_event_capacity", "rq_plan_info", "rq_plan_info_n", "rq_run_batch", "rq_replay_workspace_size",
             "rq_metrics_replay", "rq_metrics_replay_batch", "rq_oracle_workspace_size", "rq_oracle_dp", "rq_rank_table",
-            "rq_u_int", "rq_log_rows", "rq_log_expand", "rq_timing", "rq_timing_read"]
+            "rq_u_int", "rq_log_rows", "rq_log_expand", "rq_log_timeline", "rq_timing", "rq_timing_read"]

@@ -151,3 +151,81 @@ def run_significance(sim_opts, significance, time_period, seeds=range(10), rando
             _sig_reach_check(g, sim_opts.edge_list, spw, 1.0, ids[src[i, :n[i]]], bad=bad,
                              max_events=max_events)
     return _frame(res, np.tile(seeds, len(qv)), np.repeat(qv, R), "OptPW", Ks)
+
+
+def run_timeline(sim_opts, seeds=range(10), bins=None, edges=None, Ks=(1,), ctrl="opt",
+                 randomize=True, chunk_replicas=None, **run_kw):
+    """The ensemble's metrics over time: one row per bin with ``t_lo``, ``t_hi`` and, for
+    every metric (top_K..., avg_rank, r_2) and for own / other posts, the mean and the
+    standard error over the replicas, plus ``n`` (replicas averaged) and ``n_flagged``
+    (TIE / EMPTY replicas, left out).  Seed u runs as in run_grid: controller seed u and,
+    with ``randomize``, the world randomize_other_sources(u).  The seeds run in chunks of
+    ``chunk_replicas`` replicas (default: what a quarter of the free device memory holds
+    of event logs); every chunk's per-bin values are gathered on the host and reduced in
+    seed order, so the frame does not depend on the chunking.  ``run_kw`` goes to
+    Graph.run (``ctrl_rate`` for ctrl="poisson", ``q`` / ``s`` override sim_opts')."""
+    g = compiled_graph(sim_opts)
+    seeds = np.asarray(list(seeds), dtype=np.int64)
+    R = len(seeds)
+    if R < 1:
+        raise ValueError("run_timeline: no seeds")
+    kw = dict(run_kw)
+    if ctrl == "opt":
+        kw.setdefault("q", float(sim_opts.q))
+        kw.setdefault("s", sim_opts.s)
+    rate = kw.pop("ctrl_rate", None)
+    if rate is not None:
+        rate = np.broadcast_to(np.asarray(rate, dtype=np.float64), (R,))
+    if chunk_replicas is None:
+        free, _total = torch.cuda.mem_get_info()
+        probe = g.run(ctrl, n_rep=1, ctrl_seed=int(seeds[0]), world_seed=int(seeds[0]),
+                      randomize=randomize, Ks=Ks, event_log=True,
+                      **(dict(kw, ctrl_rate=rate[:1]) if rate is not None else kw))
+        per = 12 * probe.ev_t.shape[1] * 2   # capacities double on overflow reruns
+        chunk_replicas = max(1, min(R, int(free // 4 // max(1, per))))
+    chunk_replicas = max(1, int(chunk_replicas))
+    met, pst, sts = [], [], []
+    tl = None
+    for a in range(0, R, chunk_replicas):
+        sd = torch.as_tensor(seeds[a:a + chunk_replicas])
+        ck = dict(kw, ctrl_rate=rate[a:a + chunk_replicas]) if rate is not None else kw
+        res = g.run(ctrl, n_rep=len(sd), ctrl_seed=sd, world_seed=sd, randomize=randomize, Ks=Ks,
+                    event_log=True, **ck)
+        tl = res.timeline(edges=edges, bins=bins, Ks=Ks)
+        met.append(tl.metrics.cpu().numpy())
+        pst.append(tl.posts.cpu().numpy())
+        sts.append(tl.status.cpu().numpy())
+        del res
+    return timeline_frame(tl.edges, tl.Ks, np.concatenate(met), np.concatenate(pst),
+                          np.concatenate(sts))
+
+
+def timeline_frame(edges, Ks, metrics, posts, status):
+    """run_timeline's frame from per-replica values ([R, n_bins, nK + 2], [R, n_bins, 2],
+    [R]): means and standard errors (sample standard deviation / sqrt(n)) over the
+    replicas with status 0, summed in replica order."""
+    ok = np.asarray(status) == 0
+    n = int(ok.sum())
+    names = ["top_" + str(k) for k in Ks] + ["avg_rank", "r_2", "own_posts", "other_posts"]
+    vals = np.concatenate([np.asarray(metrics, dtype=np.float64)[ok],
+                           np.asarray(posts)[ok].astype(np.float64)], axis=2)
+    d = {"t_lo": np.asarray(edges[:-1]), "t_hi": np.asarray(edges[1:])}
+    nb = len(edges) - 1
+    mean = np.full((nb, len(names)), np.nan)
+    sem = np.full((nb, len(names)), np.nan)
+    if n:
+        tot = np.zeros((nb, len(names)))
+        for r in range(n):          # fixed replica order
+            tot = tot + vals[r]
+        mean = tot / n
+        if n > 1:
+            sq = np.zeros((nb, len(names)))
+            for r in range(n):
+                sq = sq + (vals[r] - mean) ** 2
+            sem = np.sqrt(sq / (n - 1)) / np.sqrt(n)
+    for i, nm in enumerate(names):
+        d[nm] = mean[:, i]
+        d[nm + "_se"] = sem[:, i]
+    d["n"] = np.full(nb, n, dtype=np.int64)
+    d["n_flagged"] = np.full(nb, len(ok) - n, dtype=np.int64)
+    return pd.DataFrame(d)

@@ -1898,6 +1898,43 @@ int rq_log_expand(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const
     return rq_launch_log_expand(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
 }
 
+int rq_log_timeline(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const int64_t* counts,
+                    int64_t n_rep, int64_t ev_cap, const double* edges, int32_t n_bins,
+                    const int32_t* Ks, int32_t nK, double* metrics, int64_t* posts,
+                    int32_t* wall_posts, int32_t* status, void* hip_stream)
+{
+    if (!g || !ev_t || !ev_src || !counts || !edges || !Ks || !metrics || !posts || !status) return RQ_EINVAL;
+    if (n_rep < 1 || n_rep > INT32_MAX || ev_cap < 1 || n_bins < 1 || nK < 1 || nK > RQ_MAX_K) return RQ_EINVAL;
+    for (int q = 0; q < nK; ++q)
+        if (Ks[q] < 1) return RQ_EINVAL;
+    // duplicate edges give one sink several rows per event (fractional pivot cells: the
+    // sequential sweep's business); the per-sink state of a replica lives in one wave's LDS
+    if (g->multi || g->n_sinks > RQ_TIMELINE_MAX_SINKS) return RQ_EUNSUPPORTED;
+    TimelineArgs a{};
+    a.ev_t = ev_t;
+    a.ev_src = ev_src;
+    a.counts = counts;
+    a.n_rep = n_rep;
+    a.ev_cap = ev_cap;
+    a.csr_ptr = g->d_csr_ptr.p;
+    a.csr_col = g->d_csr_col_el.p;
+    a.n_str = g->n_str;
+    a.n_sinks = g->n_sinks;
+    a.ctrl_idx = g->ctrl_idx;
+    a.end = g->end;
+    a.edges = edges;
+    a.n_bins = n_bins;
+    for (int q = 0; q < nK; ++q) a.Ks[q] = Ks[q];
+    a.nK = nK;
+    a.metrics = metrics;
+    a.posts = posts;
+    a.wall_posts = wall_posts;
+    a.status = status;
+    hipStream_t st = (hipStream_t)hip_stream;
+    TimedLaunch tl(K_REPLAY, st);
+    return rq_launch_timeline(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
+}
+
 }  // extern "C"
 
 extern "C" int rq_phase_clock(unsigned long long* host8)

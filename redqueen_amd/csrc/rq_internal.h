@@ -420,3 +420,24 @@ struct LogArgs {
 };
 hipError_t rq_launch_log_rows(const LogArgs& a, hipStream_t s);
 hipError_t rq_launch_log_expand(const LogArgs& a, hipStream_t s);
+
+// ---- time-resolved metrics from event logs (rq_timeline.hip) ----
+struct TimelineArgs {
+    const double* ev_t;       // [n_rep][ev_cap]
+    const int32_t* ev_src;    // [n_rep][ev_cap] stream indices
+    const int64_t* counts;    // [n_rep][4], [2] = events
+    int64_t n_rep, ev_cap;
+    const int* csr_ptr;       // [n_str + 1]
+    const int* csr_col;       // sink columns per stream (distinct within a row: no multigraph)
+    int n_str, n_sinks, ctrl_idx;
+    double end;
+    const double* edges;      // [n_bins + 1]
+    int n_bins;
+    int Ks[RQ_MAX_K];
+    int nK;
+    double* metrics;          // [n_rep][n_bins][nK + 2]
+    int64_t* posts;           // [n_rep][n_bins][2]
+    int32_t* wall_posts;      // [n_rep][n_sinks][n_bins] or null
+    int32_t* status;          // [n_rep]
+};
+hipError_t rq_launch_timeline(const TimelineArgs& a, hipStream_t s);

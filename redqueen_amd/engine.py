@@ -722,12 +722,86 @@ class BatchResult:
         rep = np.repeat(np.asarray(gids, dtype=np.int64), np.diff(ro))
         return pd.DataFrame(dict(replica=rep, **host))
 
+    def timeline(self, edges=None, bins=None, Ks=None, wall=False, stream=None):
+        """The metrics split over time bins, straight from the event logs
+        (rq_log_timeline): ``edges`` [n_bins + 1], strictly increasing and finite, or
+        ``bins`` = n equal bins over the graph's [start_time, end_time].  ``Ks``: default
+        the result's own; ``wall``: also the wall rows per (sink, bin).  Returns a
+        ``Timeline`` of device tensors; needs event_log=True."""
+        if self.ev_t is None:
+            raise ValueError("run with event_log=True to export the event log")
+        g = self.graph
+        if (edges is None) == (bins is None):
+            raise ValueError("timeline: give either edges or bins")
+        if edges is None:
+            n = int(bins)
+            if n < 1:
+                raise ValueError("timeline: bins >= 1 expected")
+            span = g.end_time - g.start_time
+            e = np.asarray([g.start_time + span * k / n for k in range(n)] + [g.end_time],
+                           dtype=np.float64)
+        else:
+            e = _arr(edges, np.float64).reshape(-1)
+        if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(e[1:] > e[:-1]):
+            raise ValueError("timeline: edges must be finite and strictly increasing")
+        ks = _arr(self.Ks if Ks is None else Ks, np.int32).reshape(-1)
+        if not 1 <= ks.size <= L.MAX_K or ks.min() < 1:
+            raise ValueError("1..%d K values >= 1" % L.MAX_K)
+        use = stream or torch.cuda.current_stream()
+        with torch.cuda.stream(use):
+            dev = self.ev_t.device
+            R, cap = self.ev_t.shape
+            nb = e.size - 1
+            ed = torch.from_numpy(e).to(dev)
+            metrics = torch.empty((R, nb, ks.size + 2), dtype=torch.float64, device=dev)
+            posts = torch.empty((R, nb, 2), dtype=torch.int64, device=dev)
+            status = torch.empty(R, dtype=torch.int32, device=dev)
+            wp = torch.empty((R, g.n_sinks, nb), dtype=torch.int32, device=dev) if wall else None
+            L.check("rq_log_timeline", L.lib().rq_log_timeline(
+                g._h, self.ev_t.data_ptr(), self.ev_src.data_ptr(), self.counts.data_ptr(), R, cap,
+                ed.data_ptr(), nb, ks.ctypes.data_as(L._pi32), ks.size, metrics.data_ptr(),
+                posts.data_ptr(), wp.data_ptr() if wall else None, status.data_ptr(),
+                use.cuda_stream))
+        return Timeline(e, ed, [int(k) for k in ks], metrics, posts, status, wp,
+                        np.sort(g.sink_ids))
+
     def events(self, i):
         """(t, src_id) numpy arrays of replica i (needs event_log=True)."""
         n = int(self.counts[i, 2].item())
         t = self.ev_t[i, :n].cpu().numpy()
         s = self.graph.stream_src_ids[self.ev_src[i, :n].cpu().numpy()]
         return t, s
+
+
+class Timeline:
+    """BatchResult.timeline's outputs: ``metrics`` [R, n_bins, nK + 2] (top_K...,
+    avg_rank, r_2: each bin's share of BatchResult.metrics), ``posts`` [R, n_bins, 2]
+    (own, other), ``status`` [R] (0, ST_TIE or ST_EMPTY: metrics NaN) and ``wall_posts``
+    [R, n_sinks, n_bins] or None, device tensors; ``edges`` (host float64) and
+    ``sink_ids``, the sink of every wall_posts row (ascending ids)."""
+
+    def __init__(self, edges, edges_dev, Ks, metrics, posts, status, wall_posts, sink_ids):
+        self.edges, self._edges_dev, self.Ks = edges, edges_dev, Ks
+        self.metrics, self.posts, self.status, self.wall_posts = metrics, posts, status, wall_posts
+        self.sink_ids = sink_ids
+
+    def top_k(self, k):
+        return self.metrics[:, :, self.Ks.index(k)]
+
+    @property
+    def avg_rank(self):
+        return self.metrics[:, :, len(self.Ks)]
+
+    @property
+    def r_2(self):
+        return self.metrics[:, :, len(self.Ks) + 1]
+
+    def wall_intensities(self):
+        """wall_posts per unit time: [R, n_sinks, n_bins] float64 (needs wall=True)."""
+        if self.wall_posts is None:
+            raise ValueError("timeline(wall=True) needed for wall intensities")
+        width = self._edges_dev[1:] - self._edges_dev[:-1]
+        return self.wall_posts.to(torch.float64) / width
 
 
 def expected_events(graph_kw):
