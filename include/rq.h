@@ -36,6 +36,9 @@
  *                       int_r_2 split over time bins         utils.py:38-56, :84-121
  *                       and the posts per (sink, segment) opt_runs.py:69-84 counts,
  *                       for every replica of an RQ_RUN_EVENT_LOG batch at once
+ *   rq_log_followers    utils.rank_of_src_in_df + the same integrals per sink column
+ *                       and int_r_2_true                     utils.py:38-56, :84-128
+ *                       for every replica of an RQ_RUN_EVENT_LOG batch at once
  *
  * Conventions
  *   - every function returns 0 (RQ_OK) or a negative rq_status; no C++
@@ -426,6 +429,47 @@ int rq_log_timeline(rq_graph_t g, const double* ev_t, const int32_t* ev_src,
                     int32_t* wall_posts,  /* device [n_rep][n_sinks][n_bins] or NULL */
                     int32_t* status,      /* device [n_rep] */
                     void* hip_stream);
+
+/* Per-follower metrics of a batch's event logs: the other axis of rank_of_src_in_df's
+ * pivot table (utils.py:38-56) -- one value per sink column where rq_log_timeline gives one
+ * per time bin -- and int_r_2_true (utils.py:84-128 are the integrals over that table).
+ * Logs, counts and ev_cap as for rq_log_timeline; the rank rule is the same.  Sink x (the
+ * graph's sinks in ascending sink-id order) holds rank_x from each of its rows to its next
+ * row, the last rank until the graph's end_time; over that seen span
+ *   vals[i][x][.] = int I(rank_x <= K-1) dt for every K, int rank_x dt, int rank_x^2 dt,
+ * each summed sequentially in time order from 0.0 as acc = acc + f(rank) * (t_next - t_row)
+ * with every product rounded (no contraction), an interval of non-positive length adding
+ * nothing: a host loop in the same order gives the same bits.  0.0 for a sink without a
+ * row.  first_t[i][x] = the time of x's first row (NaN without one); rows[i][x] (optional)
+ * = x's rows from the controlled stream and from every other stream.
+ *   r2_true[i] = int_r_2_true: with nvalid the sinks seen so far and sumR2 the exact integer
+ * sum of their rank^2 after the last event of a time t_row, summed over the distinct times
+ * in order as acc = acc + ((double)sumR2 / (double)nvalid) * (t_next - t_row), the last
+ * row until end_time.
+ *   status[i]: 0; RQ_ST_TIE when some sink got two rows at one t (vals and r2_true NaN;
+ * equal times on disjoint sinks are exact and not flagged); RQ_ST_EMPTY when no event had an
+ * edge (vals and r2_true NaN).  first_t and rows of a flagged replica are valid.  An event
+ * with a stream index outside the graph gives no row; counts[i][2] is clamped to
+ * [0, ev_cap].  One wavefront plays a replica and writes each of its output elements once
+ * (no zeroing pass, no atomics): no replica's bits depend on its neighbours or the launch.
+ *   Ks: host, 1 <= nK <= RQ_MAX_K, K >= 1; ev_cap <= 2^24 (rank^2 < 2^48, sumR2 in int64),
+ * else RQ_EINVAL.  Enqueues on hip_stream only: no allocation, no synchronisation, no
+ * workspace.
+ *   RQ_EUNSUPPORTED: a graph with duplicate edges, or with more sinks than
+ * rq_log_followers_max_sinks(nK, rows != NULL): the per-sink state -- 12 + 8 (nK + 2) bytes,
+ * 8 more with rows -- lives in one workgroup's 160 KiB of LDS (4551 sinks at nK = 1).
+ *   Added without an ABI version change (RQ_ABI_VERSION stays 6); a caller detects the
+ * functions by their symbols. */
+int rq_log_followers(rq_graph_t g, const double* ev_t, const int32_t* ev_src,
+                     const int64_t* counts, int64_t n_rep, int64_t ev_cap,
+                     const int32_t* Ks, int32_t nK,  /* host, 1 <= nK <= 4, K >= 1 */
+                     double* vals,         /* device [n_rep][n_sinks][nK + 2] */
+                     double* first_t,      /* device [n_rep][n_sinks] */
+                     int32_t* rows,        /* device [n_rep][n_sinks][2]: own, wall; or NULL */
+                     double* r2_true,      /* device [n_rep] */
+                     int32_t* status,      /* device [n_rep] */
+                     void* hip_stream);
+int32_t rq_log_followers_max_sinks(int32_t nK, int32_t with_rows);   /* 0 for a bad nK */
 
 /* Per-kernel timing for benchmarks: rq_timing(1) starts recording HIP events
  * around every kernel this library launches (on the caller's stream);

@@ -156,6 +156,10 @@ def lib():
     L.rq_log_expand.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, _P]
     L.rq_log_timeline.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int32, _pi32,
                                   C.c_int32, _P, _P, _P, _P, _P]
+    L.rq_log_followers.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int64, _pi32, C.c_int32, _P, _P,
+                                   _P, _P, _P, _P]
+    L.rq_log_followers_max_sinks.argtypes = [C.c_int32, C.c_int32]
+    L.rq_log_followers_max_sinks.restype = C.c_int32
     L.rq_timing.argtypes = [C.c_int]
     L.rq_timing_read.argtypes = [_pd, _pi64]
     for fn in ("rq_timing", "rq_timing_read", "rq_graph_build", "rq_graph_free", "rq_graph_info", "rq_graph_source_ids",
@@ -163,7 +167,7 @@ def lib():
                "rq_replay_workspace_size", "rq_metrics_replay", "rq_metrics_replay_batch",
                "rq_oracle_workspace_size",
                "rq_oracle_dp", "rq_rank_table", "rq_u_int", "rq_log_rows", "rq_log_expand",
-               "rq_log_timeline"):
+               "rq_log_timeline", "rq_log_followers"):
         getattr(L, fn).restype = C.c_int
     if L.rq_abi_version() != ABI_VERSION:
         raise ImportError("librq.so ABI version mismatch")
@@ -209,4 +213,5 @@ EXPORTED = ["rq_abi_version", "rq_strerror", "rq_graph_build", "rq_graph_free", 
             "rq_graph_source_ids", "rq_graph_followers", "rq_workspace_size",
             "rq_event_capacity", "rq_plan_info", "rq_plan_info_n", "rq_run_batch", "rq_replay_workspace_size",
             "rq_metrics_replay", "rq_metrics_replay_batch", "rq_oracle_workspace_size", "rq_oracle_dp", "rq_rank_table",
-            "rq_u_int", "rq_log_rows", "rq_log_expand", "rq_log_timeline", "rq_timing", "rq_timing_read"]
+            "rq_u_int", "rq_log_rows", "rq_log_expand", "rq_log_timeline", "rq_log_followers",
+            "rq_timing", "rq_timing_read"]   # rq_log_followers_max_sinks returns int32_t, no status

@@ -229,3 +229,78 @@ def timeline_frame(edges, Ks, metrics, posts, status):
     d["n"] = np.full(nb, n, dtype=np.int64)
     d["n_flagged"] = np.full(nb, len(ok) - n, dtype=np.int64)
     return pd.DataFrame(d)
+
+
+def run_followers(sim_opts, seeds=range(10), Ks=(1,), ctrl="opt", randomize=True,
+                  chunk_replicas=None, **run_kw):
+    """The ensemble's metrics per follower: one row per sink with ``sink_id`` and, for every
+    metric (top_K..., rank_int, rank_sq_int: the integrals over the sink's seen span) and
+    for its own / wall rows, the mean and the standard error over the replicas, plus ``n``
+    (replicas averaged) and ``n_flagged`` (TIE / EMPTY replicas, left out).  Seeds, chunks
+    and ``run_kw`` as in run_timeline: every chunk's per-sink values are gathered on the
+    host and reduced in seed order, so the frame does not depend on the chunking."""
+    g = compiled_graph(sim_opts)
+    seeds = np.asarray(list(seeds), dtype=np.int64)
+    R = len(seeds)
+    if R < 1:
+        raise ValueError("run_followers: no seeds")
+    kw = dict(run_kw)
+    if ctrl == "opt":
+        kw.setdefault("q", float(sim_opts.q))
+        kw.setdefault("s", sim_opts.s)
+    rate = kw.pop("ctrl_rate", None)
+    if rate is not None:
+        rate = np.broadcast_to(np.asarray(rate, dtype=np.float64), (R,))
+    if chunk_replicas is None:
+        free, _total = torch.cuda.mem_get_info()
+        probe = g.run(ctrl, n_rep=1, ctrl_seed=int(seeds[0]), world_seed=int(seeds[0]),
+                      randomize=randomize, Ks=Ks, event_log=True,
+                      **(dict(kw, ctrl_rate=rate[:1]) if rate is not None else kw))
+        per = 12 * probe.ev_t.shape[1] * 2   # capacities double on overflow reruns
+        chunk_replicas = max(1, min(R, int(free // 4 // max(1, per))))
+    chunk_replicas = max(1, int(chunk_replicas))
+    val, rws, sts = [], [], []
+    fl = None
+    for a in range(0, R, chunk_replicas):
+        sd = torch.as_tensor(seeds[a:a + chunk_replicas])
+        ck = dict(kw, ctrl_rate=rate[a:a + chunk_replicas]) if rate is not None else kw
+        res = g.run(ctrl, n_rep=len(sd), ctrl_seed=sd, world_seed=sd, randomize=randomize, Ks=Ks,
+                    event_log=True, **ck)
+        fl = res.followers(Ks=Ks, rows=True)
+        val.append(fl.vals.cpu().numpy())
+        rws.append(fl.rows.cpu().numpy())
+        sts.append(fl.status.cpu().numpy())
+        del res
+    return followers_frame(fl.sink_ids, fl.Ks, np.concatenate(val), np.concatenate(rws),
+                           np.concatenate(sts))
+
+
+def followers_frame(sink_ids, Ks, vals, rows, status):
+    """run_followers' frame from per-replica values ([R, n_sinks, nK + 2], [R, n_sinks, 2],
+    [R]): means and standard errors (sample standard deviation / sqrt(n)) over the
+    replicas with status 0, summed in replica order."""
+    ok = np.asarray(status) == 0
+    n = int(ok.sum())
+    names = ["top_" + str(k) for k in Ks] + ["rank_int", "rank_sq_int", "own_rows", "wall_rows"]
+    v = np.concatenate([np.asarray(vals, dtype=np.float64)[ok],
+                        np.asarray(rows)[ok].astype(np.float64)], axis=2)
+    ns = len(sink_ids)
+    d = {"sink_id": np.asarray(sink_ids, dtype=np.int64)}
+    mean = np.full((ns, len(names)), np.nan)
+    sem = np.full((ns, len(names)), np.nan)
+    if n:
+        tot = np.zeros((ns, len(names)))
+        for r in range(n):          # fixed replica order
+            tot = tot + v[r]
+        mean = tot / n
+        if n > 1:
+            sq = np.zeros((ns, len(names)))
+            for r in range(n):
+                sq = sq + (v[r] - mean) ** 2
+            sem = np.sqrt(sq / (n - 1)) / np.sqrt(n)
+    for i, nm in enumerate(names):
+        d[nm] = mean[:, i]
+        d[nm + "_se"] = sem[:, i]
+    d["n"] = np.full(ns, n, dtype=np.int64)
+    d["n_flagged"] = np.full(ns, len(ok) - n, dtype=np.int64)
+    return pd.DataFrame(d)

@@ -1935,6 +1935,49 @@ int rq_log_timeline(rq_graph_t g, const double* ev_t, const int32_t* ev_src, con
     return rq_launch_timeline(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
 }
 
+int32_t rq_log_followers_max_sinks(int32_t nK, int32_t with_rows)
+{
+    if (nK < 1 || nK > RQ_MAX_K) return 0;
+    return RQ_FOLLOWERS_LDS_BYTES / rq_followers_sink_bytes(nK, with_rows != 0);
+}
+
+int rq_log_followers(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const int64_t* counts,
+                     int64_t n_rep, int64_t ev_cap, const int32_t* Ks, int32_t nK, double* vals,
+                     double* first_t, int32_t* rows, double* r2_true, int32_t* status, void* hip_stream)
+{
+    if (!g || !ev_t || !ev_src || !counts || !Ks || !vals || !first_t || !r2_true || !status) return RQ_EINVAL;
+    // ev_cap <= 2^24 bounds every rank, so rank^2 < 2^48 and the replica's sum stays in int64
+    if (n_rep < 1 || n_rep > INT32_MAX || ev_cap < 1 || ev_cap > (1 << 24) || nK < 1 || nK > RQ_MAX_K)
+        return RQ_EINVAL;
+    for (int q = 0; q < nK; ++q)
+        if (Ks[q] < 1) return RQ_EINVAL;
+    // duplicate edges give one sink several rows per event (fractional pivot cells); the
+    // per-sink state of a replica lives in one wave's LDS
+    if (g->multi || g->n_sinks > rq_log_followers_max_sinks(nK, rows != nullptr)) return RQ_EUNSUPPORTED;
+    FollowersArgs a{};
+    a.ev_t = ev_t;
+    a.ev_src = ev_src;
+    a.counts = counts;
+    a.n_rep = n_rep;
+    a.ev_cap = ev_cap;
+    a.csr_ptr = g->d_csr_ptr.p;
+    a.csr_col = g->d_csr_col_el.p;
+    a.n_str = g->n_str;
+    a.n_sinks = g->n_sinks;
+    a.ctrl_idx = g->ctrl_idx;
+    a.end = g->end;
+    for (int q = 0; q < nK; ++q) a.Ks[q] = Ks[q];
+    a.nK = nK;
+    a.vals = vals;
+    a.first_t = first_t;
+    a.rows = rows;
+    a.r2_true = r2_true;
+    a.status = status;
+    hipStream_t st = (hipStream_t)hip_stream;
+    TimedLaunch tl(K_REPLAY, st);
+    return rq_launch_followers(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
+}
+
 }  // extern "C"
 
 extern "C" int rq_phase_clock(unsigned long long* host8)

@@ -441,3 +441,26 @@ struct TimelineArgs {
     int32_t* status;          // [n_rep]
 };
 hipError_t rq_launch_timeline(const TimelineArgs& a, hipStream_t s);
+
+// ---- per-follower metrics from event logs (rq_followers.hip) ----
+// LDS bytes of one sink's state: tlast f64 + acc[nK + 2] f64 + rank i32 (+ rows[2] i32)
+inline int rq_followers_sink_bytes(int nK, bool with_rows) { return 12 + 8 * (nK + 2) + (with_rows ? 8 : 0); }
+constexpr int RQ_FOLLOWERS_LDS_BYTES = 160 * 1024;   // one workgroup's LDS on gfx950
+struct FollowersArgs {
+    const double* ev_t;       // [n_rep][ev_cap]
+    const int32_t* ev_src;    // [n_rep][ev_cap] stream indices
+    const int64_t* counts;    // [n_rep][4], [2] = events
+    int64_t n_rep, ev_cap;
+    const int* csr_ptr;       // [n_str + 1]
+    const int* csr_col;       // sink columns per stream (distinct within a row: no multigraph)
+    int n_str, n_sinks, ctrl_idx;
+    double end;
+    int Ks[RQ_MAX_K];
+    int nK;
+    double* vals;             // [n_rep][n_sinks][nK + 2]
+    double* first_t;          // [n_rep][n_sinks]
+    int32_t* rows;            // [n_rep][n_sinks][2] or null
+    double* r2_true;          // [n_rep]
+    int32_t* status;          // [n_rep]
+};
+hipError_t rq_launch_followers(const FollowersArgs& a, hipStream_t s);

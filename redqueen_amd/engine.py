@@ -765,6 +765,33 @@ class BatchResult:
         return Timeline(e, ed, [int(k) for k in ks], metrics, posts, status, wp,
                         np.sort(g.sink_ids))
 
+    def followers(self, Ks=None, rows=False, stream=None):
+        """The metrics split over the followers, straight from the event logs
+        (rq_log_followers): per (replica, sink) the integrals of I(r <= K-1), r and r^2
+        over the sink's seen span, its first-row time and, with ``rows``, its own / wall
+        row counts; per replica int_r_2_true.  ``Ks``: default the result's own.  Returns
+        a ``Followers`` of device tensors; needs event_log=True."""
+        if self.ev_t is None:
+            raise ValueError("run with event_log=True to export the event log")
+        g = self.graph
+        ks = _arr(self.Ks if Ks is None else Ks, np.int32).reshape(-1)
+        if not 1 <= ks.size <= L.MAX_K or ks.min() < 1:
+            raise ValueError("1..%d K values >= 1" % L.MAX_K)
+        use = stream or torch.cuda.current_stream()
+        with torch.cuda.stream(use):
+            dev = self.ev_t.device
+            R, cap = self.ev_t.shape
+            vals = torch.empty((R, g.n_sinks, ks.size + 2), dtype=torch.float64, device=dev)
+            first_t = torch.empty((R, g.n_sinks), dtype=torch.float64, device=dev)
+            rw = torch.empty((R, g.n_sinks, 2), dtype=torch.int32, device=dev) if rows else None
+            r2 = torch.empty(R, dtype=torch.float64, device=dev)
+            status = torch.empty(R, dtype=torch.int32, device=dev)
+            L.check("rq_log_followers", L.lib().rq_log_followers(
+                g._h, self.ev_t.data_ptr(), self.ev_src.data_ptr(), self.counts.data_ptr(), R, cap,
+                ks.ctypes.data_as(L._pi32), ks.size, vals.data_ptr(), first_t.data_ptr(),
+                rw.data_ptr() if rows else None, r2.data_ptr(), status.data_ptr(), use.cuda_stream))
+        return Followers([int(k) for k in ks], vals, first_t, rw, r2, status, np.sort(g.sink_ids))
+
     def events(self, i):
         """(t, src_id) numpy arrays of replica i (needs event_log=True)."""
         n = int(self.counts[i, 2].item())
@@ -802,6 +829,55 @@ class Timeline:
             raise ValueError("timeline(wall=True) needed for wall intensities")
         width = self._edges_dev[1:] - self._edges_dev[:-1]
         return self.wall_posts.to(torch.float64) / width
+
+
+class Followers:
+    """BatchResult.followers' outputs: ``vals`` [R, n_sinks, nK + 2] (top_K..., the
+    integrals of r and of r^2 over every sink's seen span; 0 for a sink without a row),
+    ``first_t`` [R, n_sinks] (NaN without a row), ``rows`` [R, n_sinks, 2] (own, wall) or
+    None, ``r_2_true`` [R] (utils.int_r_2_true) and ``status`` [R] (0, ST_TIE or ST_EMPTY:
+    vals and r_2_true NaN), device tensors; ``Ks`` and ``sink_ids``, the sink of every
+    column (ascending ids)."""
+
+    def __init__(self, Ks, vals, first_t, rows, r_2_true, status, sink_ids):
+        self.Ks, self.vals, self.first_t, self.rows = Ks, vals, first_t, rows
+        self.r_2_true, self.status, self.sink_ids = r_2_true, status, sink_ids
+
+    def top_k(self, k):
+        return self.vals[:, :, self.Ks.index(k)]
+
+    @property
+    def rank_int(self):
+        return self.vals[:, :, len(self.Ks)]
+
+    @property
+    def rank_sq_int(self):
+        return self.vals[:, :, len(self.Ks) + 1]
+
+    def _per_sink(self, s):
+        """s per column of sink_ids: a scalar, a dict by sink id (a sink it does not
+        name weighs 0: Opt's s names the controlled source's followers only) or an array
+        in sink_ids order (host float64)."""
+        n = len(self.sink_ids)
+        if isinstance(s, dict):
+            return np.asarray([float(s.get(int(x), 0.0)) for x in self.sink_ids], dtype=np.float64)
+        v = np.asarray(s, dtype=np.float64)
+        if v.ndim == 0:
+            return np.full(n, float(v))
+        if v.shape != (n,):
+            raise ValueError("s: a scalar, a dict by sink id or %d values expected" % n)
+        return v
+
+    def loss(self, s):
+        """0.5 * sum_x s_x * rank_sq_int[:, x]: the significance-weighted quadratic cost
+        of every replica over each follower's seen span, [R]."""
+        w = torch.from_numpy(self._per_sink(s)).to(self.vals.device)
+        return 0.5 * (self.rank_sq_int * w).sum(1)
+
+    def u_int(self, s, q):
+        """sum_x sqrt(s_x / q) * rank_int[:, x], [R]."""
+        w = torch.from_numpy(np.sqrt(self._per_sink(s) / float(q))).to(self.vals.device)
+        return (self.rank_int * w).sum(1)
 
 
 def expected_events(graph_kw):

@@ -12,6 +12,8 @@ dataframes in one batched call (rq_metrics_replay_batch).
 
 Analysis helpers on the same footing: ``rank_of_src_in_df`` (utils.py:38-56)
 and ``u_int_opt`` (:59-81) run ``rq_rank_table`` / ``rq_u_int``;
+``int_r_2_true`` / ``calc_loss_poisson`` / ``calc_loss_opt`` (:124-167) take the
+reference's numpy expressions over ``rq_rank_table``'s table;
 ``oracle_ranking`` (:181-245) runs the oracle's O(n^2) dynamic program as
 ``rq_oracle_dp`` (one workgroup per wall, batched over walls / q values), and
 ``get_oracle_df`` / ``find_opt_oracle`` (:248-340) and ``sweep_q`` (:521-607)
@@ -310,6 +312,49 @@ def u_int_opt(df, src_id=None, end_time=None, s=None, q=None, follower_ids=None,
                                          tf.data_ptr(), tw.data_ptr(), len(fcol), float(end_time),
                                          out.data_ptr(), ws.data_ptr(), ws.numel() * 8, st))
     return np.float64(out.item())
+
+
+def int_r_2_true(df, sim_opts):
+    """Returns int avg(rank^2(t)) dt for the given source id (utils.py:124-128): the row
+    mean of the squared GPU rank table (NaN cells skipped, as pandas' mean does) times the
+    time to the next row, the last row until end_time."""
+    r_t = rank_of_src_in_df(df, sim_opts.src_id)
+    dt = np.diff(np.append(r_t.index.values, sim_opts.end_time))
+    return np.sum((r_t ** 2).mean(1) * dt)
+
+
+def _sq_rank_cost(r_t, follower_ids, s):
+    """0.5 * (rank^2 of the followers' columns) . s per pivot row.  The dot is numpy's
+    (BLAS for float64 operands: equal to ~1e-15 relative to the reference's, as u_int_opt)."""
+    return 0.5 * np.square(r_t[follower_ids].values).dot(s)
+
+
+def calc_loss_poisson(df, u_const, src_id=None, end_time=None, q=None, s=None, follower_ids=None,
+                      sim_opts=None):
+    """The loss rate of the given source at every pivot row assuming that it was Poisson
+    with rate u_const (utils.py:131-152): a Series on the GPU rank table's index."""
+    import pandas as pd
+    if sim_opts is not None:
+        src_id = mb(src_id, sim_opts.src_id)
+        end_time = mb(end_time, sim_opts.end_time)
+        q = mb(q, sim_opts.q)
+        s = mb(s, sim_opts.s)
+        follower_ids = mb(follower_ids, sim_opts.sink_ids)
+    assert is_sorted(follower_ids)
+    if s is None:
+        s = def_s_vec(len(follower_ids))
+    r_t = rank_of_src_in_df(df, src_id)
+    post_cost = 0.5 * q * np.ones(r_t.shape[0], dtype=float) * (u_const ** 2)
+    return pd.Series(data=post_cost + _sq_rank_cost(r_t, follower_ids, s), index=r_t.index)
+
+
+def calc_loss_opt(df, sim_opts):
+    """The loss rate of the given source at every pivot row assuming that it was the
+    optimal broadcaster, whose posting cost equals its rank cost (utils.py:155-167)."""
+    import pandas as pd
+    r_t = rank_of_src_in_df(df, sim_opts.src_id)
+    cost = _sq_rank_cost(r_t, sim_opts.sink_ids, sim_opts.s)
+    return pd.Series(data=cost + cost, index=r_t.index)
 
 
 # -------------------------------------------------------------------- the oracle
