@@ -39,6 +39,10 @@
  *   rq_log_followers    utils.rank_of_src_in_df + the same integrals per sink column
  *                       and int_r_2_true                     utils.py:38-56, :84-128
  *                       for every replica of an RQ_RUN_EVENT_LOG batch at once
+ *   rq_log_rank_hist    utils.rank_of_src_in_df + time_in_top_k for every K at once:
+ *                       the seen sink-time per rank value and time bin
+ *                       utils.py:38-56, :84-98 (opt_runs.py:31-33's Ks curve)
+ *                       for every replica of an RQ_RUN_EVENT_LOG batch at once
  *
  * Conventions
  *   - every function returns 0 (RQ_OK) or a negative rq_status; no C++
@@ -470,6 +474,54 @@ int rq_log_followers(rq_graph_t g, const double* ev_t, const int32_t* ev_src,
                      int32_t* status,      /* device [n_rep] */
                      void* hip_stream);
 int32_t rq_log_followers_max_sinks(int32_t nK, int32_t with_rows);   /* 0 for a bad nK */
+
+/* The rank distribution of a batch's event logs: the third axis of rank_of_src_in_df's
+ * pivot table (utils.py:38-56), the rank value itself -- per time bin, how long the seen
+ * sinks sat at rank 0, 1, 2, ...  utils.time_in_top_k (utils.py:84-98) is the sum of the
+ * first K cells, so one call gives top_K for every K <= n_ranks (rq_log_timeline: at most
+ * RQ_MAX_K per call) and the distribution avg_rank and r_2 are moments of.
+ *   Logs, counts, ev_cap, the rank rule, the time-bin rule, RQ_ST_TIE / RQ_ST_EMPTY and the
+ * clamping of counts[i][2] to [0, ev_cap] are rq_log_timeline's; an event whose stream
+ * index is outside the graph gives no row.  After the last event at a time t_row, cnt_rho
+ * is the number of seen sinks whose rank equals rho, for rho < n_ranks, and cnt_{n_ranks}
+ * is the tail: the seen sinks at rank >= n_ranks; sum over rho of cnt_rho = nvalid.  The
+ * row holds until the next event that has an edge, the last one until the graph's
+ * end_time.  With S = the sinks seen by the end of the replica,
+ *   hist[i][b][rho] = ( sum over pivot rows of
+ *                       (double)cnt_rho * |[t_row, t_next) n [edges[b], edges[b+1])| ) / (double)S
+ * each (b, rho) cell summed sequentially in time order from 0.0 as
+ * acc = acc + (double)cnt * len with the product rounded on its own (no contraction), an
+ * overlap of non-positive length adding nothing, and one division by S at the end: a host
+ * loop in that order gives the same bits (adding or skipping a term whose cnt is 0 does
+ * not change them).  Time before the first row contributes nothing and a bin no row
+ * overlaps is exactly 0.0.  Over the rank cells hist sums to the share of int nvalid dt / S
+ * that falls in the bin, and over rho < K to rq_log_timeline's top_K field, both up to
+ * rounding (the order of summation differs).
+ *   n_seen[i] = S.  max_rank[i] = the largest rank any row gave any sink (-1 for an EMPTY
+ * replica): a caller picks n_ranks > max_rank for an empty tail.  Both are valid for a TIE
+ * replica; hist is NaN for TIE and EMPTY.  No replica's output depends on its neighbours or
+ * on the launch: one wavefront plays a replica and writes each of its output elements once
+ * (no global atomics, no zeroing pass; the counts cnt are integers, so the order in which
+ * an event's sinks update them does not matter).
+ *   edges: device [n_bins + 1], strictly increasing and finite (the caller's contract, as
+ * for rq_log_timeline).  Enqueues on hip_stream only: no allocation, no synchronisation, no
+ * workspace; n_rep = 0 enqueues nothing.
+ *   RQ_EINVAL, before any HIP call: a null pointer, n_rep < 0 (or > INT32_MAX), ev_cap < 0,
+ * n_bins < 1, n_ranks outside 1..RQ_RANK_HIST_MAX_RANKS.  RQ_EUNSUPPORTED: a graph with
+ * duplicate edges, or with more than RQ_TIMELINE_MAX_SINKS sinks (the per-sink state, 8
+ * bytes, lives in one workgroup's LDS: 96 KiB at that limit, plus at most 1 KiB of counts).
+ *   Added without an ABI version change (RQ_ABI_VERSION stays 6); a caller detects the
+ * function by its symbol. */
+#define RQ_RANK_HIST_MAX_RANKS 255
+int rq_log_rank_hist(rq_graph_t g, const double* ev_t, const int32_t* ev_src,
+                     const int64_t* counts, int64_t n_rep, int64_t ev_cap,
+                     const double* edges, int32_t n_bins,   /* device [n_bins + 1] */
+                     int32_t n_ranks,                       /* 1..RQ_RANK_HIST_MAX_RANKS */
+                     double* hist,        /* device [n_rep][n_bins][n_ranks + 1] */
+                     int32_t* n_seen,     /* device [n_rep]: S */
+                     int32_t* max_rank,   /* device [n_rep] */
+                     int32_t* status,     /* device [n_rep] */
+                     void* hip_stream);
 
 /* Per-kernel timing for benchmarks: rq_timing(1) starts recording HIP events
  * around every kernel this library launches (on the caller's stream);

@@ -67,6 +67,7 @@ REPLAY_CHUNK_ROWS = 4096   # RC_L: rows per workgroup of the chunked replay
 MAX_K = 4
 MAX_RD = 64
 TIMELINE_MAX_SINKS = 12288   # RQ_TIMELINE_MAX_SINKS
+RANK_HIST_MAX_RANKS = 255    # RQ_RANK_HIST_MAX_RANKS
 
 _P = C.c_void_p
 _pd = C.POINTER(C.c_double)
@@ -159,6 +160,8 @@ def lib():
     L.rq_log_followers.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int64, _pi32, C.c_int32, _P, _P,
                                    _P, _P, _P, _P]
     L.rq_log_followers_max_sinks.argtypes = [C.c_int32, C.c_int32]
+    L.rq_log_rank_hist.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int32,
+                                   _P, _P, _P, _P, _P]
     L.rq_log_followers_max_sinks.restype = C.c_int32
     L.rq_timing.argtypes = [C.c_int]
     L.rq_timing_read.argtypes = [_pd, _pi64]
@@ -167,7 +170,7 @@ def lib():
                "rq_replay_workspace_size", "rq_metrics_replay", "rq_metrics_replay_batch",
                "rq_oracle_workspace_size",
                "rq_oracle_dp", "rq_rank_table", "rq_u_int", "rq_log_rows", "rq_log_expand",
-               "rq_log_timeline", "rq_log_followers"):
+               "rq_log_timeline", "rq_log_followers", "rq_log_rank_hist"):
         getattr(L, fn).restype = C.c_int
     if L.rq_abi_version() != ABI_VERSION:
         raise ImportError("librq.so ABI version mismatch")
@@ -214,4 +217,4 @@ EXPORTED = ["rq_abi_version", "rq_strerror", "rq_graph_build", "rq_graph_free", 
             "rq_event_capacity", "rq_plan_info", "rq_plan_info_n", "rq_run_batch", "rq_replay_workspace_size",
             "rq_metrics_replay", "rq_metrics_replay_batch", "rq_oracle_workspace_size", "rq_oracle_dp", "rq_rank_table",
             "rq_u_int", "rq_log_rows", "rq_log_expand", "rq_log_timeline", "rq_log_followers",
-            "rq_timing", "rq_timing_read"]   # rq_log_followers_max_sinks returns int32_t, no status
+            "rq_log_rank_hist", "rq_timing", "rq_timing_read"]   # rq_log_followers_max_sinks returns int32_t, no status

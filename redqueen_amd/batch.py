@@ -153,22 +153,15 @@ def run_significance(sim_opts, significance, time_period, seeds=range(10), rando
     return _frame(res, np.tile(seeds, len(qv)), np.repeat(qv, R), "OptPW", Ks)
 
 
-def run_timeline(sim_opts, seeds=range(10), bins=None, edges=None, Ks=(1,), ctrl="opt",
-                 randomize=True, chunk_replicas=None, **run_kw):
-    """The ensemble's metrics over time: one row per bin with ``t_lo``, ``t_hi`` and, for
-    every metric (top_K..., avg_rank, r_2) and for own / other posts, the mean and the
-    standard error over the replicas, plus ``n`` (replicas averaged) and ``n_flagged``
-    (TIE / EMPTY replicas, left out).  Seed u runs as in run_grid: controller seed u and,
-    with ``randomize``, the world randomize_other_sources(u).  The seeds run in chunks of
-    ``chunk_replicas`` replicas (default: what a quarter of the free device memory holds
-    of event logs); every chunk's per-bin values are gathered on the host and reduced in
-    seed order, so the frame does not depend on the chunking.  ``run_kw`` goes to
-    Graph.run (``ctrl_rate`` for ctrl="poisson", ``q`` / ``s`` override sim_opts')."""
+def _seed_chunks(sim_opts, seeds, Ks, ctrl, randomize, chunk_replicas, run_kw, what):
+    """The seed chunks of run_timeline / run_followers / run_rank_hist: yields the
+    event-logged BatchResult of every chunk of ``chunk_replicas`` seeds (default: what a
+    quarter of the free device memory holds of event logs), in seed order."""
     g = compiled_graph(sim_opts)
     seeds = np.asarray(list(seeds), dtype=np.int64)
     R = len(seeds)
     if R < 1:
-        raise ValueError("run_timeline: no seeds")
+        raise ValueError(what + ": no seeds")
     kw = dict(run_kw)
     if ctrl == "opt":
         kw.setdefault("q", float(sim_opts.q))
@@ -184,13 +177,27 @@ def run_timeline(sim_opts, seeds=range(10), bins=None, edges=None, Ks=(1,), ctrl
         per = 12 * probe.ev_t.shape[1] * 2   # capacities double on overflow reruns
         chunk_replicas = max(1, min(R, int(free // 4 // max(1, per))))
     chunk_replicas = max(1, int(chunk_replicas))
-    met, pst, sts = [], [], []
-    tl = None
     for a in range(0, R, chunk_replicas):
         sd = torch.as_tensor(seeds[a:a + chunk_replicas])
         ck = dict(kw, ctrl_rate=rate[a:a + chunk_replicas]) if rate is not None else kw
-        res = g.run(ctrl, n_rep=len(sd), ctrl_seed=sd, world_seed=sd, randomize=randomize, Ks=Ks,
+        yield g.run(ctrl, n_rep=len(sd), ctrl_seed=sd, world_seed=sd, randomize=randomize, Ks=Ks,
                     event_log=True, **ck)
+
+
+def run_timeline(sim_opts, seeds=range(10), bins=None, edges=None, Ks=(1,), ctrl="opt",
+                 randomize=True, chunk_replicas=None, **run_kw):
+    """The ensemble's metrics over time: one row per bin with ``t_lo``, ``t_hi`` and, for
+    every metric (top_K..., avg_rank, r_2) and for own / other posts, the mean and the
+    standard error over the replicas, plus ``n`` (replicas averaged) and ``n_flagged``
+    (TIE / EMPTY replicas, left out).  Seed u runs as in run_grid: controller seed u and,
+    with ``randomize``, the world randomize_other_sources(u).  The seeds run in chunks of
+    ``chunk_replicas`` replicas (default: what a quarter of the free device memory holds
+    of event logs); every chunk's per-bin values are gathered on the host and reduced in
+    seed order, so the frame does not depend on the chunking.  ``run_kw`` goes to
+    Graph.run (``ctrl_rate`` for ctrl="poisson", ``q`` / ``s`` override sim_opts')."""
+    met, pst, sts = [], [], []
+    tl = None
+    for res in _seed_chunks(sim_opts, seeds, Ks, ctrl, randomize, chunk_replicas, run_kw, "run_timeline"):
         tl = res.timeline(edges=edges, bins=bins, Ks=Ks)
         met.append(tl.metrics.cpu().numpy())
         pst.append(tl.posts.cpu().numpy())
@@ -239,33 +246,9 @@ def run_followers(sim_opts, seeds=range(10), Ks=(1,), ctrl="opt", randomize=True
     (replicas averaged) and ``n_flagged`` (TIE / EMPTY replicas, left out).  Seeds, chunks
     and ``run_kw`` as in run_timeline: every chunk's per-sink values are gathered on the
     host and reduced in seed order, so the frame does not depend on the chunking."""
-    g = compiled_graph(sim_opts)
-    seeds = np.asarray(list(seeds), dtype=np.int64)
-    R = len(seeds)
-    if R < 1:
-        raise ValueError("run_followers: no seeds")
-    kw = dict(run_kw)
-    if ctrl == "opt":
-        kw.setdefault("q", float(sim_opts.q))
-        kw.setdefault("s", sim_opts.s)
-    rate = kw.pop("ctrl_rate", None)
-    if rate is not None:
-        rate = np.broadcast_to(np.asarray(rate, dtype=np.float64), (R,))
-    if chunk_replicas is None:
-        free, _total = torch.cuda.mem_get_info()
-        probe = g.run(ctrl, n_rep=1, ctrl_seed=int(seeds[0]), world_seed=int(seeds[0]),
-                      randomize=randomize, Ks=Ks, event_log=True,
-                      **(dict(kw, ctrl_rate=rate[:1]) if rate is not None else kw))
-        per = 12 * probe.ev_t.shape[1] * 2   # capacities double on overflow reruns
-        chunk_replicas = max(1, min(R, int(free // 4 // max(1, per))))
-    chunk_replicas = max(1, int(chunk_replicas))
     val, rws, sts = [], [], []
     fl = None
-    for a in range(0, R, chunk_replicas):
-        sd = torch.as_tensor(seeds[a:a + chunk_replicas])
-        ck = dict(kw, ctrl_rate=rate[a:a + chunk_replicas]) if rate is not None else kw
-        res = g.run(ctrl, n_rep=len(sd), ctrl_seed=sd, world_seed=sd, randomize=randomize, Ks=Ks,
-                    event_log=True, **ck)
+    for res in _seed_chunks(sim_opts, seeds, Ks, ctrl, randomize, chunk_replicas, run_kw, "run_followers"):
         fl = res.followers(Ks=Ks, rows=True)
         val.append(fl.vals.cpu().numpy())
         rws.append(fl.rows.cpu().numpy())
@@ -304,3 +287,53 @@ def followers_frame(sink_ids, Ks, vals, rows, status):
     d["n"] = np.full(ns, n, dtype=np.int64)
     d["n_flagged"] = np.full(ns, len(ok) - n, dtype=np.int64)
     return pd.DataFrame(d)
+
+
+def run_rank_hist(sim_opts, seeds=range(10), ranks=64, bins=None, edges=None, ctrl="opt",
+                  randomize=True, chunk_replicas=None, **run_kw):
+    """The ensemble's rank distribution over time: one row per (time bin, rank cell) with
+    ``t_lo``, ``t_hi``, ``rank``, ``tail`` (the last cell: rank >= ``ranks``), the mean
+    ``share`` of the seen sink-time and its standard error over the replicas, plus ``n``
+    (replicas averaged) and ``n_flagged`` (TIE / EMPTY replicas, left out).  Seeds, chunks
+    and ``run_kw`` as in run_timeline; ``bins`` / ``edges`` as in BatchResult.rank_hist
+    (neither: one bin over the horizon).  Every chunk's histogram is gathered on the host
+    and reduced in seed order, so the frame does not depend on the chunking."""
+    hst, sts = [], []
+    rh = None
+    for res in _seed_chunks(sim_opts, seeds, (1,), ctrl, randomize, chunk_replicas, run_kw, "run_rank_hist"):
+        rh = res.rank_hist(ranks=ranks, edges=edges, bins=bins)
+        hst.append(rh.hist.cpu().numpy())
+        sts.append(rh.status.cpu().numpy())
+        del res
+    return rank_hist_frame(rh.edges, rh.ranks, np.concatenate(hst), np.concatenate(sts))
+
+
+def rank_hist_frame(edges, ranks, hist, status):
+    """run_rank_hist's frame from per-replica values ([R, n_bins, ranks + 1], [R]): the
+    mean and standard error (sample standard deviation / sqrt(n)) of every cell over the
+    replicas with status 0, summed in replica order.  Rows: time bins outermost, the
+    rank cells 0 .. ranks within (``tail`` marks the last)."""
+    ok = np.asarray(status) == 0
+    n = int(ok.sum())
+    ranks = int(ranks)
+    nb, nc = len(edges) - 1, ranks + 1
+    v = np.asarray(hist, dtype=np.float64).reshape(-1, nb, nc)[ok]
+    mean = np.full((nb, nc), np.nan)
+    sem = np.full((nb, nc), np.nan)
+    if n:
+        tot = np.zeros((nb, nc))
+        for r in range(n):          # fixed replica order
+            tot = tot + v[r]
+        mean = tot / n
+        if n > 1:
+            sq = np.zeros((nb, nc))
+            for r in range(n):
+                sq = sq + (v[r] - mean) ** 2
+            sem = np.sqrt(sq / (n - 1)) / np.sqrt(n)
+    cell = np.tile(np.arange(nc, dtype=np.int64), nb)
+    return pd.DataFrame({"t_lo": np.repeat(np.asarray(edges[:-1], dtype=np.float64), nc),
+                         "t_hi": np.repeat(np.asarray(edges[1:], dtype=np.float64), nc),
+                         "rank": cell, "tail": cell == ranks,
+                         "share": mean.reshape(-1), "share_se": sem.reshape(-1),
+                         "n": np.full(nb * nc, n, dtype=np.int64),
+                         "n_flagged": np.full(nb * nc, len(ok) - n, dtype=np.int64)})

@@ -1978,6 +1978,42 @@ int rq_log_followers(rq_graph_t g, const double* ev_t, const int32_t* ev_src, co
     return rq_launch_followers(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
 }
 
+int rq_log_rank_hist(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const int64_t* counts,
+                     int64_t n_rep, int64_t ev_cap, const double* edges, int32_t n_bins, int32_t n_ranks,
+                     double* hist, int32_t* n_seen, int32_t* max_rank, int32_t* status, void* hip_stream)
+{
+    if (!g || !ev_t || !ev_src || !counts || !edges || !hist || !n_seen || !max_rank || !status) return RQ_EINVAL;
+    if (n_rep < 0 || n_rep > INT32_MAX || ev_cap < 0 || n_bins < 1 || n_ranks < 1 ||
+        n_ranks > RQ_RANK_HIST_MAX_RANKS)
+        return RQ_EINVAL;
+    // duplicate edges give one sink several rows per event (fractional pivot cells); the
+    // per-sink state of a replica lives in one wave's LDS
+    if (g->multi || g->n_sinks > RQ_TIMELINE_MAX_SINKS) return RQ_EUNSUPPORTED;
+    if (n_rep == 0) return RQ_OK;   // nothing to play, nothing to write
+    RankHistArgs a{};
+    a.ev_t = ev_t;
+    a.ev_src = ev_src;
+    a.counts = counts;
+    a.n_rep = n_rep;
+    a.ev_cap = ev_cap;
+    a.csr_ptr = g->d_csr_ptr.p;
+    a.csr_col = g->d_csr_col_el.p;
+    a.n_str = g->n_str;
+    a.n_sinks = g->n_sinks;
+    a.ctrl_idx = g->ctrl_idx;
+    a.end = g->end;
+    a.edges = edges;
+    a.n_bins = n_bins;
+    a.n_ranks = n_ranks;
+    a.hist = hist;
+    a.n_seen = n_seen;
+    a.max_rank = max_rank;
+    a.status = status;
+    hipStream_t st = (hipStream_t)hip_stream;
+    TimedLaunch tl(K_REPLAY, st);
+    return rq_launch_rank_hist(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
+}
+
 }  // extern "C"
 
 extern "C" int rq_phase_clock(unsigned long long* host8)

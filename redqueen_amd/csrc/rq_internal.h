@@ -464,3 +464,23 @@ struct FollowersArgs {
     int32_t* status;          // [n_rep]
 };
 hipError_t rq_launch_followers(const FollowersArgs& a, hipStream_t s);
+
+// ---- rank distribution from event logs (rq_rank_hist.hip) ----
+struct RankHistArgs {
+    const double* ev_t;       // [n_rep][ev_cap]
+    const int32_t* ev_src;    // [n_rep][ev_cap] stream indices
+    const int64_t* counts;    // [n_rep][4], [2] = events
+    int64_t n_rep, ev_cap;
+    const int* csr_ptr;       // [n_str + 1]
+    const int* csr_col;       // sink columns per stream (distinct within a row: no multigraph)
+    int n_str, n_sinks, ctrl_idx;
+    double end;
+    const double* edges;      // [n_bins + 1]
+    int n_bins;
+    int n_ranks;              // 1..RQ_RANK_HIST_MAX_RANKS; cell n_ranks is the tail
+    double* hist;             // [n_rep][n_bins][n_ranks + 1]
+    int32_t* n_seen;          // [n_rep]
+    int32_t* max_rank;        // [n_rep]
+    int32_t* status;          // [n_rep]
+};
+hipError_t rq_launch_rank_hist(const RankHistArgs& a, hipStream_t s);

@@ -792,6 +792,48 @@ class BatchResult:
                 rw.data_ptr() if rows else None, r2.data_ptr(), status.data_ptr(), use.cuda_stream))
         return Followers([int(k) for k in ks], vals, first_t, rw, r2, status, np.sort(g.sink_ids))
 
+    def rank_hist(self, ranks=64, edges=None, bins=None, stream=None):
+        """The rank distribution over time bins, straight from the event logs
+        (rq_log_rank_hist): per (replica, bin) the seen sink-time at rank 0 .. ranks - 1
+        and, in a last cell, at rank >= ``ranks`` (the tail), each as a share of the seen
+        sinks.  ``edges`` / ``bins`` as in timeline(); with neither, one bin over the
+        graph's [start_time, end_time].  1 <= ranks <= RANK_HIST_MAX_RANKS.  Returns a
+        ``RankHist`` of device tensors; needs event_log=True."""
+        if self.ev_t is None:
+            raise ValueError("run with event_log=True to export the event log")
+        g = self.graph
+        if edges is not None and bins is not None:
+            raise ValueError("rank_hist: give edges or bins, not both")
+        if edges is None:
+            n = 1 if bins is None else int(bins)
+            if n < 1:
+                raise ValueError("rank_hist: bins >= 1 expected")
+            span = g.end_time - g.start_time
+            e = np.asarray([g.start_time + span * k / n for k in range(n)] + [g.end_time],
+                           dtype=np.float64)
+        else:
+            e = _arr(edges, np.float64).reshape(-1)
+        if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(e[1:] > e[:-1]):
+            raise ValueError("rank_hist: edges must be finite and strictly increasing")
+        nr = int(ranks)
+        if not 1 <= nr <= L.RANK_HIST_MAX_RANKS:
+            raise ValueError("rank_hist: 1 <= ranks <= %d expected" % L.RANK_HIST_MAX_RANKS)
+        use = stream or torch.cuda.current_stream()
+        with torch.cuda.stream(use):
+            dev = self.ev_t.device
+            R, cap = self.ev_t.shape
+            nb = e.size - 1
+            ed = torch.from_numpy(e).to(dev)
+            hist = torch.empty((R, nb, nr + 1), dtype=torch.float64, device=dev)
+            n_seen = torch.empty(R, dtype=torch.int32, device=dev)
+            max_rank = torch.empty(R, dtype=torch.int32, device=dev)
+            status = torch.empty(R, dtype=torch.int32, device=dev)
+            L.check("rq_log_rank_hist", L.lib().rq_log_rank_hist(
+                g._h, self.ev_t.data_ptr(), self.ev_src.data_ptr(), self.counts.data_ptr(), R, cap,
+                ed.data_ptr(), nb, nr, hist.data_ptr(), n_seen.data_ptr(), max_rank.data_ptr(),
+                status.data_ptr(), use.cuda_stream))
+        return RankHist(e, nr, hist, n_seen, max_rank, status)
+
     def events(self, i):
         """(t, src_id) numpy arrays of replica i (needs event_log=True)."""
         n = int(self.counts[i, 2].item())
@@ -829,6 +871,49 @@ class Timeline:
             raise ValueError("timeline(wall=True) needed for wall intensities")
         width = self._edges_dev[1:] - self._edges_dev[:-1]
         return self.wall_posts.to(torch.float64) / width
+
+
+class RankHist:
+    """BatchResult.rank_hist's outputs: ``hist`` [R, n_bins, ranks + 1] (the seen
+    sink-time at rank 0 .. ranks - 1 and, last, at rank >= ranks, over the replica's seen
+    sinks S: top_K is the sum of the first K cells), ``n_seen`` [R] (S), ``max_rank`` [R]
+    (the largest rank of the replica, -1 without a row: ranks > max_rank leaves the tail
+    empty) and ``status`` [R] (0, ST_TIE or ST_EMPTY: hist NaN), tensors on the run's
+    device; ``edges`` (host float64) and ``ranks``."""
+
+    def __init__(self, edges, ranks, hist, n_seen, max_rank, status):
+        self.edges, self.ranks = edges, int(ranks)
+        self.hist, self.n_seen, self.max_rank, self.status = hist, n_seen, max_rank, status
+
+    def top_k(self, k):
+        """Time in the top k per (replica, bin), [R, n_bins]: 1 <= k <= ranks."""
+        k = int(k)
+        if not 1 <= k <= self.ranks:
+            raise ValueError("top_k: 1 <= k <= %d (the histogram's ranks) expected" % self.ranks)
+        return self.hist[:, :, :k].sum(-1)
+
+    @property
+    def tail(self):
+        """The seen sink-time at rank >= ranks, [R, n_bins]."""
+        return self.hist[:, :, self.ranks]
+
+    def cdf(self):
+        """The cumulative share of the bin's seen sink-time at rank <= rho (the last
+        cell, the tail included, is 1), [R, n_bins, ranks + 1]; NaN where the bin's
+        total is 0."""
+        c = self.hist.cumsum(-1)
+        tot = c[:, :, -1:]
+        return torch.where(tot > 0, c / tot, torch.full_like(c, float("nan")))
+
+    def quantile(self, p):
+        """The smallest rho whose cdf >= p (0 < p <= 1), int64 [R, n_bins]: ``ranks``
+        means "in the tail"; -1 where the cdf is NaN."""
+        p = float(p)
+        if not 0.0 < p <= 1.0:
+            raise ValueError("quantile: 0 < p <= 1 expected")
+        c = self.cdf()
+        q = (c < p).sum(-1)
+        return torch.where(torch.isnan(c[:, :, -1]), torch.full_like(q, -1), q)
 
 
 class Followers:
