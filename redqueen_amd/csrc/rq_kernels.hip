@@ -94,13 +94,27 @@ __global__ __launch_bounds__(256) void rq_gen_streams(GenArgs a)
         // chunk (slots past n hold stale values nobody reads: readers stop at slen)
         const int r = n & (GW - 1);
         if (r > 0) {
-            // shift the staged values left by GW - r (log-steps of static shifts: no scratch)
+            // shift the staged values left by GW - r (log-steps of static shifts: no scratch).
+            // RQ_GEN_TAIL_STEPS: each step selects between two VALUES per slot, GW x log2 GW
+            // two-way selects in all.  0 (A/B): the select between two array elements, an
+            // lvalue the compiler turns into one element at a selected index -- a GW-way
+            // compare-and-select chain per output word and step
+#ifndef RQ_GEN_TAIL_STEPS
+#define RQ_GEN_TAIL_STEPS 1
+#endif
             const int sh = GW - r;
 #pragma unroll
             for (int st = 1; st < GW; st <<= 1) {
                 const bool on = (sh & st) != 0;
 #pragma unroll
-                for (int k = 0; k < GW; ++k) sb[k] = on ? sb[k + st < GW ? k + st : GW - 1] : sb[k];
+                for (int k = 0; k < GW; ++k) {
+#if RQ_GEN_TAIL_STEPS
+                    const double up = sb[k + st < GW ? k + st : GW - 1], keep = sb[k];
+                    sb[k] = on ? up : keep;
+#else
+                    sb[k] = on ? sb[k + st < GW ? k + st : GW - 1] : sb[k];
+#endif
+                }
             }
             // whole 64-byte halves, only those holding arrivals
             double4* d = reinterpret_cast<double4*>(out + (n - r));
