@@ -184,6 +184,26 @@ def _seed_chunks(sim_opts, seeds, Ks, ctrl, randomize, chunk_replicas, run_kw, w
                     event_log=True, **ck)
 
 
+def _mean_sem(v):
+    """Mean and standard error (sample standard deviation / sqrt(n)) over the n leading
+    entries of ``v`` [n, ...], summed in their order; NaN without entries, ``sem`` NaN for
+    one."""
+    n = v.shape[0]
+    mean = np.full(v.shape[1:], np.nan)
+    sem = np.full(v.shape[1:], np.nan)
+    if n:
+        tot = np.zeros(v.shape[1:])
+        for r in range(n):          # fixed replica order
+            tot = tot + v[r]
+        mean = tot / n
+        if n > 1:
+            sq = np.zeros(v.shape[1:])
+            for r in range(n):
+                sq = sq + (v[r] - mean) ** 2
+            sem = np.sqrt(sq / (n - 1)) / np.sqrt(n)
+    return mean, sem
+
+
 def run_timeline(sim_opts, seeds=range(10), bins=None, edges=None, Ks=(1,), ctrl="opt",
                  randomize=True, chunk_replicas=None, **run_kw):
     """The ensemble's metrics over time: one row per bin with ``t_lo``, ``t_hi`` and, for
@@ -218,18 +238,7 @@ def timeline_frame(edges, Ks, metrics, posts, status):
                            np.asarray(posts)[ok].astype(np.float64)], axis=2)
     d = {"t_lo": np.asarray(edges[:-1]), "t_hi": np.asarray(edges[1:])}
     nb = len(edges) - 1
-    mean = np.full((nb, len(names)), np.nan)
-    sem = np.full((nb, len(names)), np.nan)
-    if n:
-        tot = np.zeros((nb, len(names)))
-        for r in range(n):          # fixed replica order
-            tot = tot + vals[r]
-        mean = tot / n
-        if n > 1:
-            sq = np.zeros((nb, len(names)))
-            for r in range(n):
-                sq = sq + (vals[r] - mean) ** 2
-            sem = np.sqrt(sq / (n - 1)) / np.sqrt(n)
+    mean, sem = _mean_sem(vals)
     for i, nm in enumerate(names):
         d[nm] = mean[:, i]
         d[nm + "_se"] = sem[:, i]
@@ -269,18 +278,7 @@ def followers_frame(sink_ids, Ks, vals, rows, status):
                         np.asarray(rows)[ok].astype(np.float64)], axis=2)
     ns = len(sink_ids)
     d = {"sink_id": np.asarray(sink_ids, dtype=np.int64)}
-    mean = np.full((ns, len(names)), np.nan)
-    sem = np.full((ns, len(names)), np.nan)
-    if n:
-        tot = np.zeros((ns, len(names)))
-        for r in range(n):          # fixed replica order
-            tot = tot + v[r]
-        mean = tot / n
-        if n > 1:
-            sq = np.zeros((ns, len(names)))
-            for r in range(n):
-                sq = sq + (v[r] - mean) ** 2
-            sem = np.sqrt(sq / (n - 1)) / np.sqrt(n)
+    mean, sem = _mean_sem(v)
     for i, nm in enumerate(names):
         d[nm] = mean[:, i]
         d[nm + "_se"] = sem[:, i]
@@ -318,18 +316,7 @@ def rank_hist_frame(edges, ranks, hist, status):
     ranks = int(ranks)
     nb, nc = len(edges) - 1, ranks + 1
     v = np.asarray(hist, dtype=np.float64).reshape(-1, nb, nc)[ok]
-    mean = np.full((nb, nc), np.nan)
-    sem = np.full((nb, nc), np.nan)
-    if n:
-        tot = np.zeros((nb, nc))
-        for r in range(n):          # fixed replica order
-            tot = tot + v[r]
-        mean = tot / n
-        if n > 1:
-            sq = np.zeros((nb, nc))
-            for r in range(n):
-                sq = sq + (v[r] - mean) ** 2
-            sem = np.sqrt(sq / (n - 1)) / np.sqrt(n)
+    mean, sem = _mean_sem(v)
     cell = np.tile(np.arange(nc, dtype=np.int64), nb)
     return pd.DataFrame({"t_lo": np.repeat(np.asarray(edges[:-1], dtype=np.float64), nc),
                          "t_hi": np.repeat(np.asarray(edges[1:], dtype=np.float64), nc),

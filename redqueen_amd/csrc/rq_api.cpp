@@ -1898,33 +1898,54 @@ int rq_log_expand(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const
     return rq_launch_log_expand(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
 }
 
+// the LogView of a call on graph g
+static LogView log_view(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const int64_t* counts,
+                        int64_t n_rep, int64_t ev_cap)
+{
+    LogView v{};
+    v.ev_t = ev_t;
+    v.ev_src = ev_src;
+    v.counts = counts;
+    v.n_rep = n_rep;
+    v.ev_cap = ev_cap;
+    v.csr_ptr = g->d_csr_ptr.p;
+    v.csr_col = g->d_csr_col_el.p;
+    v.n_str = g->n_str;
+    v.n_sinks = g->n_sinks;
+    v.ctrl_idx = g->ctrl_idx;
+    v.end = g->end;
+    return v;
+}
+
+// 1 <= nK <= RQ_MAX_K values K >= 1 into dst; false otherwise
+static bool copy_ks(const int32_t* Ks, int32_t nK, int (&dst)[RQ_MAX_K])
+{
+    if (!Ks || nK < 1 || nK > RQ_MAX_K) return false;
+    for (int q = 0; q < nK; ++q) {
+        if (Ks[q] < 1) return false;
+        dst[q] = Ks[q];
+    }
+    return true;
+}
+
+// What no log kernel plays: duplicate edges give one sink several rows per event
+// (fractional pivot cells: the sequential sweep's business), and the per-sink state of a
+// replica lives in one wave's LDS, which max_sinks sinks fill.
+static bool log_unsupported(rq_graph_t g, int max_sinks) { return g->multi || g->n_sinks > max_sinks; }
+
 int rq_log_timeline(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const int64_t* counts,
                     int64_t n_rep, int64_t ev_cap, const double* edges, int32_t n_bins,
                     const int32_t* Ks, int32_t nK, double* metrics, int64_t* posts,
                     int32_t* wall_posts, int32_t* status, void* hip_stream)
 {
-    if (!g || !ev_t || !ev_src || !counts || !edges || !Ks || !metrics || !posts || !status) return RQ_EINVAL;
-    if (n_rep < 1 || n_rep > INT32_MAX || ev_cap < 1 || n_bins < 1 || nK < 1 || nK > RQ_MAX_K) return RQ_EINVAL;
-    for (int q = 0; q < nK; ++q)
-        if (Ks[q] < 1) return RQ_EINVAL;
-    // duplicate edges give one sink several rows per event (fractional pivot cells: the
-    // sequential sweep's business); the per-sink state of a replica lives in one wave's LDS
-    if (g->multi || g->n_sinks > RQ_TIMELINE_MAX_SINKS) return RQ_EUNSUPPORTED;
+    if (!g || !ev_t || !ev_src || !counts || !edges || !metrics || !posts || !status) return RQ_EINVAL;
+    if (n_rep < 1 || n_rep > INT32_MAX || ev_cap < 1 || n_bins < 1) return RQ_EINVAL;
     TimelineArgs a{};
-    a.ev_t = ev_t;
-    a.ev_src = ev_src;
-    a.counts = counts;
-    a.n_rep = n_rep;
-    a.ev_cap = ev_cap;
-    a.csr_ptr = g->d_csr_ptr.p;
-    a.csr_col = g->d_csr_col_el.p;
-    a.n_str = g->n_str;
-    a.n_sinks = g->n_sinks;
-    a.ctrl_idx = g->ctrl_idx;
-    a.end = g->end;
+    if (!copy_ks(Ks, nK, a.Ks)) return RQ_EINVAL;
+    if (log_unsupported(g, RQ_TIMELINE_MAX_SINKS)) return RQ_EUNSUPPORTED;
+    a.log = log_view(g, ev_t, ev_src, counts, n_rep, ev_cap);
     a.edges = edges;
     a.n_bins = n_bins;
-    for (int q = 0; q < nK; ++q) a.Ks[q] = Ks[q];
     a.nK = nK;
     a.metrics = metrics;
     a.posts = posts;
@@ -1945,28 +1966,13 @@ int rq_log_followers(rq_graph_t g, const double* ev_t, const int32_t* ev_src, co
                      int64_t n_rep, int64_t ev_cap, const int32_t* Ks, int32_t nK, double* vals,
                      double* first_t, int32_t* rows, double* r2_true, int32_t* status, void* hip_stream)
 {
-    if (!g || !ev_t || !ev_src || !counts || !Ks || !vals || !first_t || !r2_true || !status) return RQ_EINVAL;
+    if (!g || !ev_t || !ev_src || !counts || !vals || !first_t || !r2_true || !status) return RQ_EINVAL;
     // ev_cap <= 2^24 bounds every rank, so rank^2 < 2^48 and the replica's sum stays in int64
-    if (n_rep < 1 || n_rep > INT32_MAX || ev_cap < 1 || ev_cap > (1 << 24) || nK < 1 || nK > RQ_MAX_K)
-        return RQ_EINVAL;
-    for (int q = 0; q < nK; ++q)
-        if (Ks[q] < 1) return RQ_EINVAL;
-    // duplicate edges give one sink several rows per event (fractional pivot cells); the
-    // per-sink state of a replica lives in one wave's LDS
-    if (g->multi || g->n_sinks > rq_log_followers_max_sinks(nK, rows != nullptr)) return RQ_EUNSUPPORTED;
+    if (n_rep < 1 || n_rep > INT32_MAX || ev_cap < 1 || ev_cap > (1 << 24)) return RQ_EINVAL;
     FollowersArgs a{};
-    a.ev_t = ev_t;
-    a.ev_src = ev_src;
-    a.counts = counts;
-    a.n_rep = n_rep;
-    a.ev_cap = ev_cap;
-    a.csr_ptr = g->d_csr_ptr.p;
-    a.csr_col = g->d_csr_col_el.p;
-    a.n_str = g->n_str;
-    a.n_sinks = g->n_sinks;
-    a.ctrl_idx = g->ctrl_idx;
-    a.end = g->end;
-    for (int q = 0; q < nK; ++q) a.Ks[q] = Ks[q];
+    if (!copy_ks(Ks, nK, a.Ks)) return RQ_EINVAL;
+    if (log_unsupported(g, rq_log_followers_max_sinks(nK, rows != nullptr))) return RQ_EUNSUPPORTED;
+    a.log = log_view(g, ev_t, ev_src, counts, n_rep, ev_cap);
     a.nK = nK;
     a.vals = vals;
     a.first_t = first_t;
@@ -1986,22 +1992,10 @@ int rq_log_rank_hist(rq_graph_t g, const double* ev_t, const int32_t* ev_src, co
     if (n_rep < 0 || n_rep > INT32_MAX || ev_cap < 0 || n_bins < 1 || n_ranks < 1 ||
         n_ranks > RQ_RANK_HIST_MAX_RANKS)
         return RQ_EINVAL;
-    // duplicate edges give one sink several rows per event (fractional pivot cells); the
-    // per-sink state of a replica lives in one wave's LDS
-    if (g->multi || g->n_sinks > RQ_TIMELINE_MAX_SINKS) return RQ_EUNSUPPORTED;
+    if (log_unsupported(g, RQ_TIMELINE_MAX_SINKS)) return RQ_EUNSUPPORTED;
     if (n_rep == 0) return RQ_OK;   // nothing to play, nothing to write
     RankHistArgs a{};
-    a.ev_t = ev_t;
-    a.ev_src = ev_src;
-    a.counts = counts;
-    a.n_rep = n_rep;
-    a.ev_cap = ev_cap;
-    a.csr_ptr = g->d_csr_ptr.p;
-    a.csr_col = g->d_csr_col_el.p;
-    a.n_str = g->n_str;
-    a.n_sinks = g->n_sinks;
-    a.ctrl_idx = g->ctrl_idx;
-    a.end = g->end;
+    a.log = log_view(g, ev_t, ev_src, counts, n_rep, ev_cap);
     a.edges = edges;
     a.n_bins = n_bins;
     a.n_ranks = n_ranks;

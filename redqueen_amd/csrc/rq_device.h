@@ -191,6 +191,18 @@ __device__ __forceinline__ void wave_sum_u32_n(uint32_t (&v)[N])
 #undef RQ_SUM_STAGE
 }
 
+// the sum over the 64 lanes of v >= 0, in every lane: three 20-bit limbs keep every
+// 64-lane sum in 32 bits
+__device__ __forceinline__ int64_t wave_sum_i64(int64_t v)
+{
+    uint32_t limb[3] = {(uint32_t)(v & 0xFFFFF), (uint32_t)((v >> 20) & 0xFFFFF), (uint32_t)(v >> 40)};
+    wave_sum_u32_n<3>(limb);
+    const int64_t l0 = (uint32_t)__builtin_amdgcn_readlane((int)limb[0], 63);
+    const int64_t l1 = (uint32_t)__builtin_amdgcn_readlane((int)limb[1], 63);
+    const int64_t l2 = (uint32_t)__builtin_amdgcn_readlane((int)limb[2], 63);
+    return l0 + (l1 << 20) + (l2 << 40);
+}
+
 // v into lane l (v, l uniform): v_cmp + v_cndmask
 __device__ __forceinline__ int writelane(int old, int v, int l) { return lane_id() == l ? v : old; }
 // the same with v_writelane_b32: v and l must be wave-uniform

@@ -8,6 +8,7 @@
 #include <tuple>
 
 #include "../../include/rq.h"
+#include "rq_log_walk.h"
 
 // global replica id of position s of a call's replica space (rq_batch_desc.rep_lo /
 // rep_cnt): the n_grid x rep_cnt window of every grid point's n_rep replicas
@@ -421,16 +422,10 @@ struct LogArgs {
 hipError_t rq_launch_log_rows(const LogArgs& a, hipStream_t s);
 hipError_t rq_launch_log_expand(const LogArgs& a, hipStream_t s);
 
+// ---- the log kernels: each args block starts with the LogView of rq_log_walk.h ----
 // ---- time-resolved metrics from event logs (rq_timeline.hip) ----
 struct TimelineArgs {
-    const double* ev_t;       // [n_rep][ev_cap]
-    const int32_t* ev_src;    // [n_rep][ev_cap] stream indices
-    const int64_t* counts;    // [n_rep][4], [2] = events
-    int64_t n_rep, ev_cap;
-    const int* csr_ptr;       // [n_str + 1]
-    const int* csr_col;       // sink columns per stream (distinct within a row: no multigraph)
-    int n_str, n_sinks, ctrl_idx;
-    double end;
+    LogView log;
     const double* edges;      // [n_bins + 1]
     int n_bins;
     int Ks[RQ_MAX_K];
@@ -447,14 +442,7 @@ hipError_t rq_launch_timeline(const TimelineArgs& a, hipStream_t s);
 inline int rq_followers_sink_bytes(int nK, bool with_rows) { return 12 + 8 * (nK + 2) + (with_rows ? 8 : 0); }
 constexpr int RQ_FOLLOWERS_LDS_BYTES = 160 * 1024;   // one workgroup's LDS on gfx950
 struct FollowersArgs {
-    const double* ev_t;       // [n_rep][ev_cap]
-    const int32_t* ev_src;    // [n_rep][ev_cap] stream indices
-    const int64_t* counts;    // [n_rep][4], [2] = events
-    int64_t n_rep, ev_cap;
-    const int* csr_ptr;       // [n_str + 1]
-    const int* csr_col;       // sink columns per stream (distinct within a row: no multigraph)
-    int n_str, n_sinks, ctrl_idx;
-    double end;
+    LogView log;
     int Ks[RQ_MAX_K];
     int nK;
     double* vals;             // [n_rep][n_sinks][nK + 2]
@@ -467,14 +455,7 @@ hipError_t rq_launch_followers(const FollowersArgs& a, hipStream_t s);
 
 // ---- rank distribution from event logs (rq_rank_hist.hip) ----
 struct RankHistArgs {
-    const double* ev_t;       // [n_rep][ev_cap]
-    const int32_t* ev_src;    // [n_rep][ev_cap] stream indices
-    const int64_t* counts;    // [n_rep][4], [2] = events
-    int64_t n_rep, ev_cap;
-    const int* csr_ptr;       // [n_str + 1]
-    const int* csr_col;       // sink columns per stream (distinct within a row: no multigraph)
-    int n_str, n_sinks, ctrl_idx;
-    double end;
+    LogView log;
     const double* edges;      // [n_bins + 1]
     int n_bins;
     int n_ranks;              // 1..RQ_RANK_HIST_MAX_RANKS; cell n_ranks is the tail

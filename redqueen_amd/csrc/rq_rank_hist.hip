@@ -4,10 +4,9 @@
 // of that table, after time (rq_timeline.hip) and the followers (rq_followers.hip).
 // utils.time_in_top_k (utils.py:84-98) is the sum of the first K cells.
 //
-// One wavefront per replica, one block per wavefront: the walk of rq_timeline.hip.  The
-// wave replays the replica's (t, stream) log in order against state private to it in LDS:
-//   rank[x]   the controlled source's rank in sink x's feed (-1: no row yet): an own row
-//             sets 0, any other row adds 1 (unseen -> 1);
+// One wavefront per replica, one block per wavefront.  The wave replays the replica's
+// (t, stream) log in order (log_walk, rq_log_walk.h) against state private to it in LDS:
+//   rank[x]   the controlled source's rank in sink x's feed (-1: no row yet; next_rank);
 //   grp[x]    the time group of x's last row: a second row of x in the same group is a
 //             duplicate (t, sink) pivot cell (RQ_ST_TIE);
 //   cnt[c]    seen sinks at rank c for c < n_ranks, at rank >= n_ranks for c = n_ranks
@@ -17,35 +16,25 @@
 // atomics, whose result does not depend on their order.  An own row sends every touched
 // sink to cell 0, which gets one add of the ballots' popcount per event; a move within
 // the tail touches nothing.  No f64 is ever accumulated with an atomic.
-//   The row holds until the next event with an edge, so cnt is constant on
-// [t_row, t_next) and the interval is clipped to the bins it meets.  Lane l owns the
-// cells l, l + 64, ... (NB = 1, 2 or 4 per lane: the template parameter, so the open
-// bin's sums stay in registers); at each event it reads its cells and adds cnt * len.
-// Events come in time order: the open bin only moves forward and is stored once, when it
-// closes, 64 consecutive cells per store -- every output element is written exactly once
-// by its replica's wave, whatever n_bins (no global atomics, no zeroing pass, no
-// dependence on the launch geometry).  When the replica ends (S = its seen sinks is
-// known) the wave divides its own values, or overwrites them with NaN for a TIE / EMPTY
-// replica.
-//
-// Loads: event times, streams and CSR row bounds are fetched 64 events at a time, one
-// chunk ahead; the first 64 sink columns of the next event are fetched while the
-// current one is applied.
+//   cnt is constant between two events with an edge and is clipped to the bins it meets
+// (BinClip).  Lane l owns the cells l, l + 64, ... (NB = 1, 2 or 4 per lane: the template
+// parameter, so the open bin's sums stay in registers); at each event it reads its cells
+// and adds cnt * len.  A closing bin is stored 64 consecutive cells per store -- every
+// output element is written exactly once by its replica's wave, whatever n_bins (no
+// global atomics, no zeroing pass, no dependence on the launch geometry).  When the
+// replica ends (S = its seen sinks is known) the wave divides its own values, or
+// overwrites them with NaN for a TIE / EMPTY replica.
 #include <hip/hip_runtime.h>
 
 #include "rq_device.h"
 #include "rq_internal.h"
+#include "rq_log_walk.h"
 
 #pragma clang fp contract(off)
 
 using namespace rq;
 
 namespace {
-
-struct RhChunk {   // lane l: event k0 + l of the replica (an event past the log, or of a
-    double t;      // stream index outside the graph, has an empty row: p0 == p1)
-    int j, p0, p1;
-};
 
 __device__ __forceinline__ void cell_add(int* p, int v)
 {
@@ -58,7 +47,7 @@ __global__ __launch_bounds__(64) void rq_rank_hist_k(RankHistArgs a)
     extern __shared__ __attribute__((aligned(16))) int lds_rh[];
     const int lane = lane_id();
     const int64_t r = blockIdx.x;
-    const int NS = a.n_sinks;
+    const int NS = a.log.n_sinks;
     const int nb = a.n_bins;
     const int NR = a.n_ranks;   // cells 0..NR-1: that rank; cell NR: the tail
     const int NC = NR + 1;      // <= NB * 64
@@ -73,10 +62,6 @@ __global__ __launch_bounds__(64) void rq_rank_hist_k(RankHistArgs a)
     for (int q = 0; q < NB; ++q) cnt[lane + 64 * q] = 0;
     wave_lds_sync();
 
-    int64_t n = a.counts[r * 4 + 2];
-    n = n < 0 ? 0 : (n > a.ev_cap ? a.ev_cap : n);
-    const double* T = a.ev_t + r * a.ev_cap;
-    const int32_t* J = a.ev_src + r * a.ev_cap;
     double* H = a.hist + r * nb * NC;
 
     int nvalid = 0;   // seen sinks
@@ -85,121 +70,63 @@ __global__ __launch_bounds__(64) void rq_rank_hist_k(RankHistArgs a)
     double cur_t = 0.0;
     int g = 0;   // time group of cur_t
     // the open bin and this lane's cells of it
-    int b = 0;
-    double e0 = a.edges[0], e1 = a.edges[1];
+    BinClip clip(a.edges, nb);
     double acc[NB];
 #pragma unroll
     for (int q = 0; q < NB; ++q) acc[q] = 0.0;
 
-    auto close_bin = [&]() {   // store bin b, open b + 1
+    auto store_bin = [&](int b) {
 #pragma unroll
         for (int q = 0; q < NB; ++q) {
             const int c = lane + 64 * q;
             if (c < NC) H[(int64_t)b * NC + c] = acc[q];
-            acc[q] = 0.0;
-        }
-        ++b;
-        if (b < nb) {
-            e0 = a.edges[b];
-            e1 = a.edges[b + 1];
         }
     };
-    // the held row over [cur_t, hi), then every bin that ends at or before hi closes
-    auto advance = [&](double hi) {
-        double f[NB];
+    auto held = [&](double (&f)[NB]) {   // this lane's cells of the held row
 #pragma unroll
         for (int q = 0; q < NB; ++q) f[q] = have ? (double)cnt[lane + 64 * q] : 0.0;
-        while (b < nb) {
-            if (have) {
-                const double lo = cur_t > e0 ? cur_t : e0;
-                const double up = hi < e1 ? hi : e1;
-                if (up > lo) {
-                    const double len = up - lo;
-#pragma unroll
-                    for (int q = 0; q < NB; ++q) acc[q] = acc[q] + f[q] * len;
+    };
+
+    log_walk(a.log, r, [&](double t, bool own, int p0, int p1, int xfirst) {
+        double f[NB];
+        held(f);   // reads cnt: the previous event ended with wave_lds_sync
+        clip.advance(have, cur_t, t, f, acc, store_bin);
+        if (!have || t != cur_t) ++g;
+        have = true;
+        cur_t = t;
+        int dv = 0, to0 = 0;
+        uint64_t dup = 0;
+        for (int e = p0; e < p1; e += 64) {
+            const bool act = e + lane < p1;
+            const int x = row_sink(a.log, e, p0, act, xfirst);
+            const int rk = act ? rank[x] : 0;
+            const int gx = act ? grp[x] : -1;
+            const int nr = next_rank(own, rk);
+            if (act) {
+                rank[x] = nr;
+                grp[x] = g;
+                mx = nr > mx ? nr : mx;
+                if (own) {
+                    if (rk > 0) cell_add(cnt + (rk < NR ? rk : NR), -1);
+                } else if (rk < NR) {   // a move within the tail touches nothing
+                    if (rk >= 0) cell_add(cnt + rk, -1);
+                    cell_add(cnt + (nr < NR ? nr : NR), 1);
                 }
             }
-            if (!(e1 <= hi)) break;
-            close_bin();
+            dup |= __ballot(act && gx == g);
+            dv += popc(__ballot(act && rk < 0));
+            if (own) to0 += popc(__ballot(act && rk != 0));   // rk == 0 stays in cell 0
         }
-    };
-
-    auto load_chunk = [&](int64_t k0) {
-        RhChunk c;
-        c.t = 0.0;
-        c.j = -1;
-        c.p0 = c.p1 = 0;
-        const int64_t k = k0 + lane;
-        if (k < n) {
-            c.t = T[k];
-            const int j = J[k];
-            if ((unsigned)j < (unsigned)a.n_str) {
-                c.j = j;
-                c.p0 = a.csr_ptr[j];
-                c.p1 = a.csr_ptr[j + 1];
-            }
-        }
-        return c;
-    };
-
-    RhChunk A = load_chunk(0);
-    int xcur = 0;
+        if (to0 && lane == 0) cell_add(cnt, to0);
+        wave_lds_sync();
+        if (dup) tie = true;
+        nvalid += dv;
+    });
     {
-        const int q0 = bcast_i(A.p0, 0), q1 = bcast_i(A.p1, 0);
-        if (q0 + lane < q1) xcur = a.csr_col[q0 + lane];
+        double f[NB];
+        held(f);
+        clip.finish(have, cur_t, a.log.end, f, acc, store_bin);
     }
-    for (int64_t k0 = 0; k0 < n; k0 += 64) {
-        const RhChunk B = load_chunk(k0 + 64);
-        const int cnt_ev = (int)((n - k0) < 64 ? (n - k0) : 64);
-        for (int i = 0; i < cnt_ev; ++i) {
-            const double t = bcast_d(A.t, i);
-            const int j = bcast_i(A.j, i);
-            const int p0 = bcast_i(A.p0, i), p1 = bcast_i(A.p1, i);
-            // the next event's first 64 sink columns, in flight while this one is applied
-            const int q0 = i < 63 ? bcast_i(A.p0, i + 1) : bcast_i(B.p0, 0);
-            const int q1 = i < 63 ? bcast_i(A.p1, i + 1) : bcast_i(B.p1, 0);
-            int xnext = 0;
-            if (q0 + lane < q1) xnext = a.csr_col[q0 + lane];
-            if (p1 > p0) {
-                advance(t);   // reads cnt: the previous event ended with wave_lds_sync
-                if (!have || t != cur_t) ++g;
-                have = true;
-                cur_t = t;
-                const bool own = j == a.ctrl_idx;
-                int dv = 0, to0 = 0;
-                uint64_t dup = 0;
-                for (int e = p0; e < p1; e += 64) {
-                    const bool act = e + lane < p1;
-                    const int x = e == p0 ? xcur : (act ? a.csr_col[e + lane] : 0);
-                    const int rk = act ? rank[x] : 0;
-                    const int gx = act ? grp[x] : -1;
-                    const int nr = own ? 0 : (rk < 0 ? 1 : rk + 1);
-                    if (act) {
-                        rank[x] = nr;
-                        grp[x] = g;
-                        mx = nr > mx ? nr : mx;
-                        if (own) {
-                            if (rk > 0) cell_add(cnt + (rk < NR ? rk : NR), -1);
-                        } else if (rk < NR) {   // a move within the tail touches nothing
-                            if (rk >= 0) cell_add(cnt + rk, -1);
-                            cell_add(cnt + (nr < NR ? nr : NR), 1);
-                        }
-                    }
-                    dup |= __ballot(act && gx == g);
-                    dv += popc(__ballot(act && rk < 0));
-                    if (own) to0 += popc(__ballot(act && rk != 0));   // rk == 0 stays in cell 0
-                }
-                if (to0 && lane == 0) cell_add(cnt, to0);
-                wave_lds_sync();
-                if (dup) tie = true;
-                nvalid += dv;
-            }
-            xcur = xnext;
-        }
-        A = B;
-    }
-    advance(a.end);   // the last row holds until end_time
-    while (b < nb) close_bin();
 
     // S is known now: normalise, or blank a replica without a table.  Every lane reloads
     // the cells it stored itself; the fence completes the stores first.
@@ -229,7 +156,7 @@ __global__ __launch_bounds__(64) void rq_rank_hist_k(RankHistArgs a)
         mx = m > mx ? m : mx;
     }
     if (lane == 0) {
-        a.status[r] = tie ? RQ_ST_TIE : (!have ? RQ_ST_EMPTY : 0);
+        a.status[r] = log_status(have, tie);
         a.n_seen[r] = nvalid;
         a.max_rank[r] = mx;
     }
@@ -238,8 +165,8 @@ __global__ __launch_bounds__(64) void rq_rank_hist_k(RankHistArgs a)
 template <int NB>
 hipError_t launch_nb(const RankHistArgs& a, hipStream_t s)
 {
-    const size_t lds = ((size_t)a.n_sinks * 2 + NB * 64) * sizeof(int);
-    const dim3 grid((unsigned)a.n_rep), block(64);
+    const size_t lds = ((size_t)a.log.n_sinks * 2 + NB * 64) * sizeof(int);
+    const dim3 grid((unsigned)a.log.n_rep), block(64);
     hipLaunchKernelGGL((rq_rank_hist_k<NB>), grid, block, lds, s, a);
     return hipGetLastError();
 }

@@ -5,8 +5,7 @@
 //
 // One wavefront per replica, one block per wavefront.  The wave replays the replica's
 // (t, stream) log in order against per-sink state private to it in LDS:
-//   rank[x]   the controlled source's rank in sink x's feed (-1: no row yet) -- the rule
-//             of rq_sweep_core.h: an own row sets 0, any other row adds 1 (unseen -> 1);
+//   rank[x]   the controlled source's rank in sink x's feed (-1: no row yet; next_rank);
 //   grp[x]    the time group of x's last row: a second row of x in the same group is a
 //             duplicate (t, sink) pivot cell (RQ_ST_TIE);
 //   wcnt[x]   (wall_posts only) wall rows of x in the current bin.
@@ -21,24 +20,21 @@
 // (S = its seen sinks is known) the wave divides its own values, or overwrites them
 // with NaN for a TIE / EMPTY replica.
 //
-// Loads: event times, streams and CSR row bounds are fetched 64 events at a time, one
-// chunk ahead; the first 64 sink columns of the next event are fetched while the
-// current one is applied.
+// The log reader and the bin clipper stand here in their own copy, the text of log_walk
+// and BinClip (rq_log_walk.h): through the shared templates this kernel's one-K
+// instantiation measured 3 to 4 % slower on C3.  A fix to either
+// goes into both places.
 #include <hip/hip_runtime.h>
 
 #include "rq_device.h"
 #include "rq_internal.h"
+#include "rq_log_walk.h"
 
 #pragma clang fp contract(off)
 
 using namespace rq;
 
 namespace {
-
-struct TlChunk {   // lane l: event k0 + l of the replica (an event past the log, or of a
-    double t;      // stream index outside the graph, has an empty row: p0 == p1)
-    int j, p0, p1;
-};
 
 template <int NK, bool WALL>
 __global__ __launch_bounds__(64) void rq_timeline_k(TimelineArgs a)
@@ -47,7 +43,7 @@ __global__ __launch_bounds__(64) void rq_timeline_k(TimelineArgs a)
     constexpr int NV = NK + 2;
     const int lane = lane_id();
     const int64_t r = blockIdx.x;
-    const int NS = a.n_sinks;
+    const int NS = a.log.n_sinks;
     const int nb = a.n_bins;
     int* rank = lds_tl;
     int* grp = lds_tl + NS;
@@ -59,10 +55,10 @@ __global__ __launch_bounds__(64) void rq_timeline_k(TimelineArgs a)
     }
     wave_lds_sync();
 
-    int64_t n = a.counts[r * 4 + 2];
-    n = n < 0 ? 0 : (n > a.ev_cap ? a.ev_cap : n);
-    const double* T = a.ev_t + r * a.ev_cap;
-    const int32_t* J = a.ev_src + r * a.ev_cap;
+    int64_t n = a.log.counts[r * 4 + 2];
+    n = n < 0 ? 0 : (n > a.log.ev_cap ? a.log.ev_cap : n);
+    const double* T = a.log.ev_t + r * a.log.ev_cap;
+    const int32_t* J = a.log.ev_src + r * a.log.ev_cap;
     double* M = a.metrics + r * nb * NV;
     int64_t* P = a.posts + r * nb * 2;
     int32_t* W = WALL ? a.wall_posts + r * NS * (int64_t)nb : nullptr;
@@ -132,7 +128,7 @@ __global__ __launch_bounds__(64) void rq_timeline_k(TimelineArgs a)
     };
 
     auto load_chunk = [&](int64_t k0) {
-        TlChunk c;
+        LogChunk c;
         c.t = 0.0;
         c.j = -1;
         c.p0 = c.p1 = 0;
@@ -140,23 +136,23 @@ __global__ __launch_bounds__(64) void rq_timeline_k(TimelineArgs a)
         if (k < n) {
             c.t = T[k];
             const int j = J[k];
-            if ((unsigned)j < (unsigned)a.n_str) {
+            if ((unsigned)j < (unsigned)a.log.n_str) {
                 c.j = j;
-                c.p0 = a.csr_ptr[j];
-                c.p1 = a.csr_ptr[j + 1];
+                c.p0 = a.log.csr_ptr[j];
+                c.p1 = a.log.csr_ptr[j + 1];
             }
         }
         return c;
     };
 
-    TlChunk A = load_chunk(0);
+    LogChunk A = load_chunk(0);
     int xcur = 0;
     {
         const int q0 = bcast_i(A.p0, 0), q1 = bcast_i(A.p1, 0);
-        if (q0 + lane < q1) xcur = a.csr_col[q0 + lane];
+        if (q0 + lane < q1) xcur = a.log.csr_col[q0 + lane];
     }
     for (int64_t k0 = 0; k0 < n; k0 += 64) {
-        const TlChunk B = load_chunk(k0 + 64);
+        const LogChunk B = load_chunk(k0 + 64);
         const int cnt = (int)((n - k0) < 64 ? (n - k0) : 64);
         for (int i = 0; i < cnt; ++i) {
             const double t = bcast_d(A.t, i);
@@ -166,13 +162,13 @@ __global__ __launch_bounds__(64) void rq_timeline_k(TimelineArgs a)
             const int q0 = i < 63 ? bcast_i(A.p0, i + 1) : bcast_i(B.p0, 0);
             const int q1 = i < 63 ? bcast_i(A.p1, i + 1) : bcast_i(B.p1, 0);
             int xnext = 0;
-            if (q0 + lane < q1) xnext = a.csr_col[q0 + lane];
+            if (q0 + lane < q1) xnext = a.log.csr_col[q0 + lane];
             if (p1 > p0) {
                 advance(t);
                 if (!have || t != cur_t) ++g;
                 have = true;
                 cur_t = t;
-                const bool own = j == a.ctrl_idx;
+                const bool own = j == a.log.ctrl_idx;
                 const bool inbin = b < nb && e0 <= t;   // t < e1: advance closed the bins before
                 if (inbin) {
                     if (own) ++p_own;
@@ -185,10 +181,10 @@ __global__ __launch_bounds__(64) void rq_timeline_k(TimelineArgs a)
                 uint64_t dup = 0;
                 for (int e = p0; e < p1; e += 64) {
                     const bool act = e + lane < p1;
-                    const int x = e == p0 ? xcur : (act ? a.csr_col[e + lane] : 0);
+                    const int x = e == p0 ? xcur : (act ? a.log.csr_col[e + lane] : 0);
                     const int rk = act ? rank[x] : 0;
                     const int gx = act ? grp[x] : -1;
-                    const int nr = own ? 0 : (rk < 0 ? 1 : rk + 1);
+                    const int nr = next_rank(own, rk);
                     if (act) {
                         rank[x] = nr;
                         grp[x] = g;
@@ -207,24 +203,14 @@ __global__ __launch_bounds__(64) void rq_timeline_k(TimelineArgs a)
                 nvalid += dv;
 #pragma unroll
                 for (int q = 0; q < NK; ++q) cK[q] += dK[q];
-                if (own) {
-                    // < 2^31 per sink: three 20-bit limbs keep every 64-lane sum in 32 bits
-                    uint32_t limb[3] = {(uint32_t)(rsum & 0xFFFFF), (uint32_t)((rsum >> 20) & 0xFFFFF),
-                                        (uint32_t)(rsum >> 40)};
-                    wave_sum_u32_n<3>(limb);
-                    const int64_t l0 = (uint32_t)__builtin_amdgcn_readlane((int)limb[0], 63);
-                    const int64_t l1 = (uint32_t)__builtin_amdgcn_readlane((int)limb[1], 63);
-                    const int64_t l2 = (uint32_t)__builtin_amdgcn_readlane((int)limb[2], 63);
-                    sumR -= l0 + (l1 << 20) + (l2 << 40);
-                } else {
-                    sumR += p1 - p0;
-                }
+                if (own) sumR -= wave_sum_i64(rsum);   // < 2^31 per sink
+                else sumR += p1 - p0;
             }
             xcur = xnext;
         }
         A = B;
     }
-    advance(a.end);   // the last row holds until end_time
+    advance(a.log.end);   // the last row holds until end_time
     while (b < nb) close_bin();
 
     // S is known now: normalise the top-K sums, or blank a replica without a table.  The
@@ -242,14 +228,14 @@ __global__ __launch_bounds__(64) void rq_timeline_k(TimelineArgs a)
             M[k] = v / S;
         }
     }
-    if (lane == 0) a.status[r] = tie ? RQ_ST_TIE : (!have ? RQ_ST_EMPTY : 0);
+    if (lane == 0) a.status[r] = log_status(have, tie);
 }
 
 template <int NK>
 hipError_t launch_nk(const TimelineArgs& a, hipStream_t s)
 {
-    const size_t lds = (size_t)a.n_sinks * (a.wall_posts ? 3 : 2) * sizeof(int);
-    const dim3 grid((unsigned)a.n_rep), block(64);
+    const size_t lds = (size_t)a.log.n_sinks * (a.wall_posts ? 3 : 2) * sizeof(int);
+    const dim3 grid((unsigned)a.log.n_rep), block(64);
     if (a.wall_posts) hipLaunchKernelGGL((rq_timeline_k<NK, true>), grid, block, lds, s, a);
     else hipLaunchKernelGGL((rq_timeline_k<NK, false>), grid, block, lds, s, a);
     return hipGetLastError();

@@ -638,6 +638,28 @@ class Graph:
         return int(info[0])
 
 
+def _log_edges(what, graph, edges, bins, default_bins):
+    """The time-bin edges of a log metric as float64: ``edges``, or ``bins`` equal bins over
+    the graph's [start_time, end_time].  With neither, ``default_bins`` bins; None demands
+    one of the two."""
+    if default_bins is None and (edges is None) == (bins is None):
+        raise ValueError(what + ": give either edges or bins")
+    if edges is not None and bins is not None:
+        raise ValueError(what + ": give edges or bins, not both")
+    if edges is None:
+        n = default_bins if bins is None else int(bins)
+        if n < 1:
+            raise ValueError(what + ": bins >= 1 expected")
+        span = graph.end_time - graph.start_time
+        e = np.asarray([graph.start_time + span * k / n for k in range(n)] + [graph.end_time],
+                       dtype=np.float64)
+    else:
+        e = _arr(edges, np.float64).reshape(-1)
+    if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(e[1:] > e[:-1]):
+        raise ValueError(what + ": edges must be finite and strictly increasing")
+    return e
+
+
 class BatchResult:
     """Per-replica outputs (torch tensors on the device), replica i = g * n_rep + r."""
 
@@ -722,31 +744,28 @@ class BatchResult:
         rep = np.repeat(np.asarray(gids, dtype=np.int64), np.diff(ro))
         return pd.DataFrame(dict(replica=rep, **host))
 
+    def _log_graph(self):
+        """The graph of timeline / followers / rank_hist, which need the event logs."""
+        if self.ev_t is None:
+            raise ValueError("run with event_log=True to export the event log")
+        return self.graph
+
+    def _log_ks(self, Ks):
+        """The K values of a log metric as int32: ``Ks``, default the result's own."""
+        ks = _arr(self.Ks if Ks is None else Ks, np.int32).reshape(-1)
+        if not 1 <= ks.size <= L.MAX_K or ks.min() < 1:
+            raise ValueError("1..%d K values >= 1" % L.MAX_K)
+        return ks
+
     def timeline(self, edges=None, bins=None, Ks=None, wall=False, stream=None):
         """The metrics split over time bins, straight from the event logs
         (rq_log_timeline): ``edges`` [n_bins + 1], strictly increasing and finite, or
         ``bins`` = n equal bins over the graph's [start_time, end_time].  ``Ks``: default
         the result's own; ``wall``: also the wall rows per (sink, bin).  Returns a
         ``Timeline`` of device tensors; needs event_log=True."""
-        if self.ev_t is None:
-            raise ValueError("run with event_log=True to export the event log")
-        g = self.graph
-        if (edges is None) == (bins is None):
-            raise ValueError("timeline: give either edges or bins")
-        if edges is None:
-            n = int(bins)
-            if n < 1:
-                raise ValueError("timeline: bins >= 1 expected")
-            span = g.end_time - g.start_time
-            e = np.asarray([g.start_time + span * k / n for k in range(n)] + [g.end_time],
-                           dtype=np.float64)
-        else:
-            e = _arr(edges, np.float64).reshape(-1)
-        if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(e[1:] > e[:-1]):
-            raise ValueError("timeline: edges must be finite and strictly increasing")
-        ks = _arr(self.Ks if Ks is None else Ks, np.int32).reshape(-1)
-        if not 1 <= ks.size <= L.MAX_K or ks.min() < 1:
-            raise ValueError("1..%d K values >= 1" % L.MAX_K)
+        g = self._log_graph()
+        e = _log_edges("timeline", g, edges, bins, None)
+        ks = self._log_ks(Ks)
         use = stream or torch.cuda.current_stream()
         with torch.cuda.stream(use):
             dev = self.ev_t.device
@@ -771,12 +790,8 @@ class BatchResult:
         over the sink's seen span, its first-row time and, with ``rows``, its own / wall
         row counts; per replica int_r_2_true.  ``Ks``: default the result's own.  Returns
         a ``Followers`` of device tensors; needs event_log=True."""
-        if self.ev_t is None:
-            raise ValueError("run with event_log=True to export the event log")
-        g = self.graph
-        ks = _arr(self.Ks if Ks is None else Ks, np.int32).reshape(-1)
-        if not 1 <= ks.size <= L.MAX_K or ks.min() < 1:
-            raise ValueError("1..%d K values >= 1" % L.MAX_K)
+        g = self._log_graph()
+        ks = self._log_ks(Ks)
         use = stream or torch.cuda.current_stream()
         with torch.cuda.stream(use):
             dev = self.ev_t.device
@@ -799,22 +814,8 @@ class BatchResult:
         sinks.  ``edges`` / ``bins`` as in timeline(); with neither, one bin over the
         graph's [start_time, end_time].  1 <= ranks <= RANK_HIST_MAX_RANKS.  Returns a
         ``RankHist`` of device tensors; needs event_log=True."""
-        if self.ev_t is None:
-            raise ValueError("run with event_log=True to export the event log")
-        g = self.graph
-        if edges is not None and bins is not None:
-            raise ValueError("rank_hist: give edges or bins, not both")
-        if edges is None:
-            n = 1 if bins is None else int(bins)
-            if n < 1:
-                raise ValueError("rank_hist: bins >= 1 expected")
-            span = g.end_time - g.start_time
-            e = np.asarray([g.start_time + span * k / n for k in range(n)] + [g.end_time],
-                           dtype=np.float64)
-        else:
-            e = _arr(edges, np.float64).reshape(-1)
-        if e.size < 2 or not np.all(np.isfinite(e)) or not np.all(e[1:] > e[:-1]):
-            raise ValueError("rank_hist: edges must be finite and strictly increasing")
+        g = self._log_graph()
+        e = _log_edges("rank_hist", g, edges, bins, 1)
         nr = int(ranks)
         if not 1 <= nr <= L.RANK_HIST_MAX_RANKS:
             raise ValueError("rank_hist: 1 <= ranks <= %d expected" % L.RANK_HIST_MAX_RANKS)

@@ -7,6 +7,7 @@ value is a sum of at most n non-negative terms of at most 4 roundings each, so w
 the summation order |got - exp| <= (n + 8) * 2**-52 * |exp| with n the replica's pivot
 rows; a value whose expectation is 0 must be exactly 0.0; integer outputs must be equal.
 Every output buffer of a raw call carries a 64-element sentinel guard."""
+import functools
 import math
 import types
 
@@ -15,79 +16,13 @@ import pytest
 
 from tests import followers_ref as FR
 from tests import timeline_ref as TR
+from tests.loghelp import (ctx as _ctx, degrees_world as _degrees_world, graph as _graph, pack,
+                           raw_followers as _raw, raw_followers_dev as _raw_dev)
 
 pytestmark = pytest.mark.gpu
-GUARD = 64
-D_SENT, I_SENT = -1.2345e300, -7777
+_pack = functools.partial(pack, full=True)   # a log may fill its row here
 
 
-def _ctx():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from redqueen_amd import _lib as L
-    from redqueen_amd import engine, graphs
-    return torch, L, engine, graphs
-
-
-def _graph(engine, so, **kw):
-    return engine.Graph(so["src_id"], so["other_sources"], so["sink_ids"], so["edge_list"],
-                        so["end_time"], **kw)
-
-
-def _raw_dev(torch, L, g, dt, ds, dc, Ks, rows=True, expect=0):
-    """rq_log_followers on device arrays; outputs come back as numpy, their guard tails
-    checked.  Returns dict(vals, first_t, rows or None, r2_true, status)."""
-    R, cap = dt.shape
-    nK, NS = len(Ks), g.n_sinks
-    n_v, n_f, n_r = R * NS * (nK + 2), R * NS, R * NS * 2
-    val = torch.full((n_v + GUARD,), D_SENT, dtype=torch.float64, device="cuda")
-    fst = torch.full((n_f + GUARD,), D_SENT, dtype=torch.float64, device="cuda")
-    r2 = torch.full((R + GUARD,), D_SENT, dtype=torch.float64, device="cuda")
-    sta = torch.full((R + GUARD,), I_SENT, dtype=torch.int32, device="cuda")
-    rw = torch.full((n_r + GUARD,), I_SENT, dtype=torch.int32, device="cuda") if rows else None
-    ks = np.asarray(Ks, dtype=np.int32)
-    rc = L.lib().rq_log_followers(g._h, dt.data_ptr(), ds.data_ptr(), dc.data_ptr(), R, cap,
-                                  ks.ctypes.data_as(L._pi32), nK, val.data_ptr(), fst.data_ptr(),
-                                  rw.data_ptr() if rows else None, r2.data_ptr(), sta.data_ptr(),
-                                  torch.cuda.current_stream().cuda_stream)
-    assert rc == expect, rc
-    torch.cuda.synchronize()
-    val, fst, r2, sta = val.cpu().numpy(), fst.cpu().numpy(), r2.cpu().numpy(), sta.cpu().numpy()
-    assert (val[n_v:] == D_SENT).all() and (fst[n_f:] == D_SENT).all()
-    assert (r2[R:] == D_SENT).all() and (sta[R:] == I_SENT).all()
-    out = dict(vals=val[:n_v].reshape(R, NS, nK + 2), first_t=fst[:n_f].reshape(R, NS), rows=None,
-               r2_true=r2[:R], status=sta[:R])
-    if rows:
-        w = rw.cpu().numpy()
-        assert (w[n_r:] == I_SENT).all()
-        out["rows"] = w[:n_r].reshape(R, NS, 2)
-    if expect != 0:   # a refused call launches nothing
-        assert (val == D_SENT).all() and (sta == I_SENT).all()
-    return out
-
-
-def _raw(torch, L, g, ev_t, ev_src, counts, Ks, rows=True, expect=0):
-    dt = torch.from_numpy(np.ascontiguousarray(ev_t, dtype=np.float64)).cuda()
-    ds = torch.from_numpy(np.ascontiguousarray(ev_src, dtype=np.int32)).cuda()
-    dc = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.int64)).cuda()
-    return _raw_dev(torch, L, g, dt, ds, dc, Ks, rows, expect)
-
-
-def _pack(logs, cap, g):
-    """(ev_t, ev_src, counts) of event lists [(t, src_id arrays)]: the tail of every
-    replica's row holds NaN and -1 and must not be read."""
-    R = len(logs)
-    ev_t = np.full((R, cap), np.nan)
-    ev_src = np.full((R, cap), -1, dtype=np.int32)
-    counts = np.full((R, 4), -5, dtype=np.int64)
-    idx = {int(s): k for k, s in enumerate(g.stream_src_ids)}
-    for i, (t, s) in enumerate(logs):
-        assert len(t) == len(s) <= cap
-        ev_t[i, :len(t)] = t
-        ev_src[i, :len(t)] = [idx[int(x)] for x in s]
-        counts[i, 2] = len(t)
-    return ev_t, ev_src, counts
 
 
 def _assert_replica(out, i, ref, what, rows=True):
@@ -138,7 +73,7 @@ def _fixture_expected(f, name, nK):
 
 # ------------------------------------------------------------- 1. fixture logs, raw ABI
 def test_fixture_logs_through_the_raw_abi(golden):
-    torch, L, engine, graphs = _ctx()
+    torch, _O, L, engine, graphs = _ctx()
     f = golden("followers.npz")
     Ks = [int(k) for k in f["Ks"]]
     for name in (str(n) for n in f["names"]):
@@ -159,7 +94,7 @@ def test_fixture_logs_through_the_raw_abi(golden):
 # ------------------------------------------------- 2. README graph, every controller
 @pytest.mark.parametrize("ctrl", ["opt", "poisson", "wall", "times"])
 def test_readme_graph_every_controller(ctrl):
-    torch, L, engine, graphs = _ctx()
+    torch, _O, L, engine, graphs = _ctx()
     so = graphs.readme()
     Ks = (1, 2, 33)
     R = 16
@@ -200,20 +135,9 @@ def test_readme_graph_every_controller(ctrl):
 
 
 # ------------------------------------------------------------------- 3. wide rows
-def _degrees_world():
-    """Out-degrees 1, 63, 64, 65 (wall sources) and 129 (the controlled source) over 140
-    sinks, edge list shuffled."""
-    sinks = list(range(3000, 3140))
-    edges = ([(2, sinks[139])] + [(3, x) for x in sinks[:63]] + [(4, x) for x in sinks[20:84]] +
-             [(5, x) for x in sinks[70:135]] + [(1, x) for x in sinks[5:134]])
-    edges = [edges[i] for i in np.random.RandomState(6).permutation(len(edges))]
-    return dict(src_id=1, end_time=6.0, q=400.0, s=1.0, sink_ids=sinks, edge_list=edges,
-                other_sources=[("Poisson", {"src_id": k, "seed": k, "rate": 4.0}) for k in (2, 3, 4, 5)])
-
-
 @pytest.mark.parametrize("world", ["degrees", "c3_short"])
 def test_wide_rows(world):
-    torch, L, engine, graphs = _ctx()
+    torch, _O, L, engine, graphs = _ctx()
     if world == "degrees":
         so, R, Ks = _degrees_world(), 5, (1, 3)
     else:   # C3's 1000 followers (the controlled source reaches all of them): 36 KB of LDS
@@ -241,7 +165,7 @@ TIE_WORLD = dict(src_id=1, end_time=20.0, sink_ids=[10, 11, 12, 13],
 
 def test_realdata_tie_world():
     """Two RealData sources post at t = 5 and both reach sink 10."""
-    torch, L, engine, graphs = _ctx()
+    torch, _O, L, engine, graphs = _ctx()
     so = dict(src_id=1, end_time=20.0, sink_ids=[10, 11, 12],
               edge_list=[(1, 10), (2, 10), (2, 11), (3, 10), (3, 12)],
               other_sources=[("RealData", {"src_id": 2, "times": [1.0, 5.0, 9.0]}),
@@ -260,7 +184,7 @@ def test_realdata_tie_world():
 
 
 def test_hand_made_ties_and_empty():
-    torch, L, engine, graphs = _ctx()
+    torch, _O, L, engine, graphs = _ctx()
     so = TIE_WORLD
     g = _graph(engine, so)
     Ks = (1, 2)
@@ -293,7 +217,7 @@ def test_hand_made_ties_and_empty():
 
 # ------------------------------------------------------------------ 5. determinism
 def test_same_bits_alone_permuted_and_without_rows():
-    torch, L, engine, graphs = _ctx()
+    torch, _O, L, engine, graphs = _ctx()
     so = graphs.readme()
     g = _graph(engine, so)
     R, Ks = 8, (1, 2)
@@ -327,7 +251,7 @@ def test_same_bits_alone_permuted_and_without_rows():
 
 # ------------------------------------------------ 6. clamping and bad stream indices
 def test_counts_are_clamped_and_bad_streams_give_no_row():
-    torch, L, engine, graphs = _ctx()
+    torch, _O, L, engine, graphs = _ctx()
     so = TIE_WORLD
     g = _graph(engine, so)
     Ks = (1, 2)
@@ -355,7 +279,7 @@ def test_counts_are_clamped_and_bad_streams_give_no_row():
 
 # ------------------------------------------------------------------- 7. validation
 def test_validation():
-    torch, L, engine, graphs = _ctx()
+    torch, _O, L, engine, graphs = _ctx()
     g = _graph(engine, TIE_WORLD)
     lib = L.lib()
     buf = torch.zeros(4096, dtype=torch.float64, device="cuda")
@@ -390,7 +314,7 @@ def test_validation():
 def test_sink_limit():
     """rq_log_followers_max_sinks(4, 1) sinks run (the per-sink state of one replica fills
     one workgroup's LDS); one more is refused with rows and fits without them."""
-    torch, L, engine, graphs = _ctx()
+    torch, _O, L, engine, graphs = _ctx()
     lib = L.lib()
     N = int(lib.rq_log_followers_max_sinks(4, 1))
     assert 1000 < N < int(lib.rq_log_followers_max_sinks(4, 0)) < int(lib.rq_log_followers_max_sinks(1, 0))
@@ -419,7 +343,7 @@ def test_sink_limit():
 
 # ------------------------------------------------- 8. Followers helpers, run_followers
 def test_loss_and_u_int_helpers():
-    torch, L, engine, graphs = _ctx()
+    torch, _O, L, engine, graphs = _ctx()
     so = graphs.mixed()
     g = _graph(engine, so)
     R = 6
@@ -446,7 +370,7 @@ def test_loss_and_u_int_helpers():
 
 
 def test_run_followers_matches_one_batch_and_any_chunking():
-    torch, L, engine, graphs = _ctx()
+    torch, _O, L, engine, graphs = _ctx()
     import pandas as pd
     from redqueen_amd import batch
     from redqueen_amd.opt_model import SimOpts
@@ -470,7 +394,7 @@ def test_run_followers_matches_one_batch_and_any_chunking():
 
 # --------------------------------------------------------------- 9. the utils facade
 def test_utils_losses_against_the_reference(golden):
-    torch, L, engine, graphs = _ctx()
+    torch, _O, L, engine, graphs = _ctx()
     import pandas as pd
     from redqueen_amd import utils
     f = golden("followers.npz")

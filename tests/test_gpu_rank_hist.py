@@ -15,82 +15,19 @@ import numpy as np
 import pytest
 
 from tests import rank_hist_ref as RH
+from tests.loghelp import (ctx as _ctx, graph as _graph, pack as _pack, raw_rank_hist as _raw,
+                           same_bits as _same_bits)
 
 pytestmark = pytest.mark.gpu
-GUARD = 64
-D_SENT, I_SENT = -1.2345e300, -7777
 NRS = (1, 63, 64, 65, 127, 128, 255)   # 64, 65, 128, 129 and 256 cells: 1, 2 and 4 per lane
-
-
-def _ctx():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from oracle import oracle as O
-    from redqueen_amd import _lib as L
-    from redqueen_amd import engine, graphs
-    return torch, O, L, engine, graphs
-
-
-def _graph(engine, so, **kw):
-    return engine.Graph(so["src_id"], so["other_sources"], so["sink_ids"], so["edge_list"],
-                        so["end_time"], **kw)
 
 
 def _dummy(ids):
     return [("Poisson2", {"src_id": int(s), "seed": 1, "rate": 1.0}) for s in ids]
 
 
-def _raw(torch, L, g, ev_t, ev_src, counts, edges, nr, expect=0, cap=None):
-    """rq_log_rank_hist on host arrays; outputs come back as numpy, their guard tails
-    checked.  Returns (hist, n_seen, max_rank, status)."""
-    R = ev_t.shape[0]
-    cap = ev_t.shape[1] if cap is None else cap
-    nb = len(edges) - 1
-    dt = torch.from_numpy(np.ascontiguousarray(ev_t)).cuda()
-    ds = torch.from_numpy(np.ascontiguousarray(ev_src, dtype=np.int32)).cuda()
-    dc = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.int64)).cuda()
-    de = torch.from_numpy(np.ascontiguousarray(edges, dtype=np.float64)).cuda()
-    n_h = R * nb * (nr + 1)
-    hist = torch.full((n_h + GUARD,), D_SENT, dtype=torch.float64, device="cuda")
-    ints = [torch.full((R + GUARD,), I_SENT, dtype=torch.int32, device="cuda") for _ in range(3)]
-    rc = L.lib().rq_log_rank_hist(g._h, dt.data_ptr(), ds.data_ptr(), dc.data_ptr(), R, cap,
-                                  de.data_ptr(), nb, nr, hist.data_ptr(), ints[0].data_ptr(),
-                                  ints[1].data_ptr(), ints[2].data_ptr(),
-                                  torch.cuda.current_stream().cuda_stream)
-    assert rc == expect, rc
-    torch.cuda.synchronize()
-    hist = hist.cpu().numpy()
-    ints = [v.cpu().numpy() for v in ints]
-    assert (hist[n_h:] == D_SENT).all() and all((v[R:] == I_SENT).all() for v in ints)
-    if expect != 0:
-        assert (hist == D_SENT).all() and all((v == I_SENT).all() for v in ints)
-    return hist[:n_h].reshape(R, nb, nr + 1), ints[0][:R], ints[1][:R], ints[2][:R]
-
-
-def _pack(logs, cap, g):
-    """(ev_t, ev_src, counts) of event lists [(t, src_id arrays)]: the tail of every
-    replica's row holds NaN and -1 and must not be read."""
-    R = len(logs)
-    ev_t = np.full((R, cap), np.nan)
-    ev_src = np.full((R, cap), -1, dtype=np.int32)
-    counts = np.full((R, 4), -5, dtype=np.int64)
-    idx = {int(s): k for k, s in enumerate(g.stream_src_ids)}
-    for i, (t, s) in enumerate(logs):
-        assert len(t) == len(s) < cap
-        ev_t[i, :len(t)] = t
-        ev_src[i, :len(t)] = [idx[int(x)] for x in s]
-        counts[i, 2] = len(t)
-    return ev_t, ev_src, counts
-
-
 def _csr(g):
     return RH.csr_of(g.stream_src_ids, g.sink_ids, g._edges)
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
 
 
 def _assert_close(got, exp, rows, what):

@@ -10,72 +10,10 @@ import numpy as np
 import pytest
 
 from tests import timeline_ref as TR
+from tests.loghelp import (ctx as _ctx, graph as _graph, pack as _pack, raw_timeline as _raw,
+                           same_bits as _same_bits)
 
 pytestmark = pytest.mark.gpu
-GUARD = 64
-D_SENT, I_SENT = -1.2345e300, -7777
-
-
-def _ctx():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from oracle import oracle as O
-    from redqueen_amd import _lib as L
-    from redqueen_amd import engine, graphs
-    return torch, O, L, engine, graphs
-
-
-def _graph(engine, so, **kw):
-    return engine.Graph(so["src_id"], so["other_sources"], so["sink_ids"], so["edge_list"],
-                        so["end_time"], **kw)
-
-
-def _raw(torch, L, g, ev_t, ev_src, counts, edges, Ks, wall=False, expect=0):
-    """rq_log_timeline on host arrays; outputs come back as numpy, their guard tails
-    checked.  Returns (metrics, posts, status, wall_posts or None)."""
-    R, cap = ev_t.shape
-    nb, nK = len(edges) - 1, len(Ks)
-    dt = torch.from_numpy(np.ascontiguousarray(ev_t)).cuda()
-    ds = torch.from_numpy(np.ascontiguousarray(ev_src, dtype=np.int32)).cuda()
-    dc = torch.from_numpy(np.ascontiguousarray(counts, dtype=np.int64)).cuda()
-    de = torch.from_numpy(np.ascontiguousarray(edges, dtype=np.float64)).cuda()
-    n_m, n_p, n_w = R * nb * (nK + 2), R * nb * 2, R * g.n_sinks * nb
-    met = torch.full((n_m + GUARD,), D_SENT, dtype=torch.float64, device="cuda")
-    pst = torch.full((n_p + GUARD,), I_SENT, dtype=torch.int64, device="cuda")
-    sta = torch.full((R + GUARD,), I_SENT, dtype=torch.int32, device="cuda")
-    wp = torch.full((n_w + GUARD,), I_SENT, dtype=torch.int32, device="cuda") if wall else None
-    ks = np.asarray(Ks, dtype=np.int32)
-    rc = L.lib().rq_log_timeline(g._h, dt.data_ptr(), ds.data_ptr(), dc.data_ptr(), R, cap,
-                                 de.data_ptr(), nb, ks.ctypes.data_as(L._pi32), nK, met.data_ptr(),
-                                 pst.data_ptr(), wp.data_ptr() if wall else None, sta.data_ptr(),
-                                 torch.cuda.current_stream().cuda_stream)
-    assert rc == expect, rc
-    torch.cuda.synchronize()
-    met, pst, sta = met.cpu().numpy(), pst.cpu().numpy(), sta.cpu().numpy()
-    assert (met[n_m:] == D_SENT).all() and (pst[n_p:] == I_SENT).all() and (sta[R:] == I_SENT).all()
-    w = None
-    if wall:
-        w = wp.cpu().numpy()
-        assert (w[n_w:] == I_SENT).all()
-        w = w[:n_w].reshape(R, g.n_sinks, nb)
-    return met[:n_m].reshape(R, nb, nK + 2), pst[:n_p].reshape(R, nb, 2), sta[:R], w
-
-
-def _pack(logs, cap, g):
-    """(ev_t, ev_src, counts) of event lists [(t, src_id arrays)]: the tail of every
-    replica's row holds NaN and -1 and must not be read."""
-    R = len(logs)
-    ev_t = np.full((R, cap), np.nan)
-    ev_src = np.full((R, cap), -1, dtype=np.int32)
-    counts = np.full((R, 4), -5, dtype=np.int64)
-    idx = {int(s): k for k, s in enumerate(g.stream_src_ids)}
-    for i, (t, s) in enumerate(logs):
-        assert len(t) == len(s) < cap
-        ev_t[i, :len(t)] = t
-        ev_src[i, :len(t)] = [idx[int(x)] for x in s]
-        counts[i, 2] = len(t)
-    return ev_t, ev_src, counts
 
 
 def _assert_close(got, exp, rows, what):
@@ -258,10 +196,6 @@ def test_hand_made_ties_and_empty():
     assert (sta2 == 0).all()
     for i in (0, 2, 4):
         assert _same_bits(met[i], met2[i]) and np.array_equal(pst[i], pst2[i]) and np.array_equal(w[i], w2[i])
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
 
 
 # ------------------------------------------------------------------ 5. determinism
