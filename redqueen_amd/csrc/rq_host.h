@@ -1,0 +1,266 @@
+// rq_host.h -- the host core of librq: graph topology, environment knobs, the planner and
+// the controller tables.  Pure host arithmetic: this header, rq_topo.cpp and rq_plan.cpp
+// build with any C++17 compiler and no ROCm include path (tests/host/plan_check.cpp does).
+// rq_internal.h includes it, so the kernels and rq_api.cpp share the constants and
+// SweepInst below.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/rq.h"
+
+// ---- constants the planner and the kernels share ----
+#define RQ_MAX_STREAMS 2048   // 512 per fast instance (8 per lane); LOG instances 16 / 32 per lane
+#define RQ_NPSUM1_LDS 516   // doubles of wave_npsum<1> scratch (== rq::npsum_lds_doubles<1>())
+// threads per block of the merged-stream sweep instances (1024: <= 128 VGPRs)
+#ifndef RQ_MRG_LB
+#define RQ_MRG_LB 1024
+#endif
+#define RQ_MG_B 512         // merge block: one source per thread (the fast general sweep: <= 512)
+// merged entries carry the stream as u16 (+ a u8 of its high bits past 65535 streams);
+// the two-level merge takes up to RQ_MG_B groups of RQ_MG_B streams
+#define RQ_MAX_STREAMS_MRG (RQ_MG_B * RQ_MG_B)
+
+// The sweep template instance a plan selects, one field per template axis.  The planner
+// builds it from a Plan (sweep_inst: its candidates, rq_plan_info and the launch alike);
+// each kernel file resolves it to the kernel in one place (sweep_kernel / fw_kernel), which
+// the launch and the occupancy query share.  The flags name the kernels' template
+// parameters (the rq_kernels and rq_sweep_fw kernel files).
+struct SweepInst {
+    bool fused;   // rq_sweep_fw / rq_sweep_fwm (<= 64 sources), else the general rq_sweep
+    int nK;       // K variants (1..RQ_MAX_K)
+    bool col16;   // sink columns in LDS as uint16, else read from global memory as int
+    bool log;     // the sequential sweep (event log, max_events, duplicate edges, ties)
+    bool gs;      // log: the per-sink state in global memory (SweepArgs.gs)
+    bool bits;    // K = 1 on per-stream sink bitsets
+    bool bl;      // K = 1 on per-wave LDS sink bits (general sweep)
+    bool mrg;     // plays the merged streams of rq_merge_streams; else:
+    int spl;      //   general: sources per lane, 1 / 2 / 4 / 8 (log: 1 / 8 / 16 / 32)
+    int W;        //   fused: depth of the generated arrival rings, 32 / 16 / 8 (the general
+                  //   instances fix theirs: a window of 4; log: rings of 8, 4 at 32 per lane)
+    bool gt;      // mrg, general: the per-stream tables in global memory
+    bool pw;      // fused: the OptPWSignificance controller
+    bool pair;    // fused, mrg: the RedQueen controller's draws by call pairs (one Philox call per
+                  //   lane every other tile, both of its draws used), else a call per draw
+    bool scan;    // fused, mrg: the wave that swept a replica integrates its rows itself (rq_scan's
+                  //   sums, written to SweepArgs.metrics; no rq_scan launch for the chunk)
+};
+// SweepInst.scan: the per-wave LDS of the sweep's scan, aliased on the wave's sweep area
+// (dead after the tile loop, initialised again at the top of each replica); the layout of
+// rq::npsum_lds_doubles<nK + 2, RQ_FWS_NL>() -- 66 leaf slots, a block of 8192 rows has <= 65
+#define RQ_FWS_NL 66
+#define RQ_FWS_LDS_BYTES(nK) ((size_t)8 * (((nK) + 2 + 3) * RQ_FWS_NL + 4))
+
+// ---- the planner's three questions to the device ----
+// Defined next to the kernels (the rq_kernels and rq_sweep_fw files); a program that links the
+// host core without them supplies its own.
+// blocks of 64 * wpb threads per CU the instance reaches with `lds` bytes of dynamic LDS
+// (rq_occupancy); <= 0: no instance or no device -- the planner takes the LDS bound
+int rq_sweep_blocks_per_cu(const SweepInst& i, int wpb, size_t lds);
+// the fused pair of rq_sweep_blocks_per_cu (SweepInst.fused)
+int rq_fw_blocks_per_cu(const SweepInst& i, int wpb, size_t lds);
+int rq_cu_count();   // CUs of the current device (256 on MI355X when the query fails)
+
+namespace rqh {
+
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// ---- environment knobs ----
+// Everything a plan or a launch depends on besides its arguments.  read_knobs() reads the
+// environment once per ABI call (tests and bench.py flip knobs between runs of one process);
+// the planner and the run loop take the struct and never call getenv themselves.
+template <class T>
+struct Knob {   // a knob whose unset default depends on the plan or the call
+    bool set = false;
+    T v{};
+};
+struct Knobs {
+    // -- the planner (make_plan and the workspace budget) --
+    // RQ_WS_BUDGET_GB: caps the workspace budget, GiB (include/rq.h documents it for users)
+    Knob<double> ws_budget_gb;
+    // RQ_CAP_SQUEEZE: scales the merged-sequence / pivot-row capacities down, clamped to
+    // [0.01, 1]; tests only (test_gpu_engine, test_gpu_reruns, test_gpu_sweep_scan: undersized
+    // capacities exercise the overflow reruns)
+    double cap_squeeze = 1.0;
+    // RQ_MG_GRP: streams per first-level merge group, 64 or RQ_MG_B; A/B (scripts/dev/ab_grp.sh)
+    Knob<int> mg_grp;
+    // RQ_MRG=0: the general fast sweep merges the per-source streams itself; A/B only
+    bool mrg = true;
+    // RQ_G_COLLDS: force the general sweep's column placement (1 LDS, 0 global); tuning only
+    Knob<int> g_collds;
+    // RQ_G_W: only this ring depth for the general sweep (0: any); tuning only
+    int g_w = 0;
+    // RQ_SKIP=0: no played-stream skipping in the K = 1 sink-bit sweep; A/B, test_gpu_graphs
+    bool skip = true;
+    // RQ_FWM=0: the fused sweep generates its arrivals in-kernel; A/B only
+    bool fwm = true;
+    // RQ_CTRL_DRAWS=0: a Philox call per controller draw instead of call pairs; A/B and
+    // tests (test_gpu_ctrl_draws, test_gpu_draws_ahead, test_gpu_sweep_scan)
+    bool ctrl_draws = true;
+    // RQ_SWEEP_SCAN=0: the scan kernel instead of the sweep's own scan; A/B, test_gpu_sweep_scan
+    bool sweep_scan = true;
+    // RQ_FW_W: only this ring depth for the fused sweep (0: any); tuning (scripts/gpu_envab.sh)
+    // and test_gpu_policy
+    int fw_w = 0;
+    // RQ_PIPE: streams of the pipelined chunk loop, clamped to 1..3; bench.py sets 1 for its
+    // per-kernel times; A/B (scripts/bench_paths.py, scripts/gpu_ab_env.sh, scripts/dev/ab5.sh,
+    // ab_c5.sh)
+    int pipe = 2;
+    // RQ_PIPE_CHUNK: replicas per pipelined chunk, at least 64; A/B only
+    Knob<int64_t> pipe_chunk;
+    // RQ_ORDER=1: longest-first replica order for the sweep; A/B and test_gpu_merge
+    bool order = false;
+
+    // -- rq_run_batch (the sweep's launch arguments) --
+    // RQ_SWEEP_DBG: SweepArgs.dbg, skips sweep phases; profiling only (scripts/gpu_dbg.sh,
+    // gpu_breakdown.sh, c5_phase.py)
+    int sweep_dbg = 0;
+    // RQ_FW_TILE: arrivals a fused tile aims at; tuning and test_gpu_policy
+    double fw_tile = 58.0;   // measured on C3: 40 -> 895k, 48 -> 943k, 58 -> 964k, 62 -> 956k replicas/s
+    // RQ_FW_HMIN / RQ_FW_THR / RQ_FW_HFILL: the fused sweep's refill policy (clamped against
+    // the plan where they are used); tuning and test_gpu_policy
+    Knob<int> fw_hmin, fw_thr, fw_hfill;
+    // RQ_FW_STATIC: nonzero = no replica work queue (one replica per wave); read once per
+    // process; A/B only (scripts/c5_rate.py)
+    int fw_static = 0;
+    // RQ_CLK_MERGE: RQ_PHASE_CLOCK builds only, the merge's phase clocks instead of the
+    // sweep's (scripts/dev/merge_clock.py)
+    bool clk_merge = false;
+
+    // -- rp_run (dataframe replay) --
+    // RQ_RP_CHUNK: force the chunked replay on (nonzero) or off (0); A/B, test_gpu_replay_chunked,
+    // scripts/bench_paths.py, redqueen_amd/utils.py's docs
+    Knob<int> rp_chunk;
+    // RQ_RP_SMALL=0: no small-table first tier for one K; A/B only
+    bool rp_small = true;
+    // RQ_CLK_REPLAY: RQ_PHASE_CLOCK builds only, rq_rp_fast's phase clocks (scripts/dev/replay_clock.py)
+    bool clk_replay = false;
+};
+Knobs read_knobs();
+
+// ---- graph topology: the host half of an rq_graph ----
+struct GraphTopo {
+    int n_str = 0, ctrl_idx = -1, n_sinks = 0, n_fol = 0;
+    int64_t n_edges = 0, ctrl_src_id = 0;
+    double start = 0.0, end = 0.0;
+    // per stream (dynamic sources by src_id, then static ones by src_id); the controlled
+    // slot has kind RQ_SRC_NONE
+    std::vector<int64_t> src_id;
+    std::vector<int> kind, orig_idx, arr_off, arr_n;
+    std::vector<int> is_static;   // 1: a static source (equal times play after the dynamic ones)
+    std::vector<uint32_t> seed;
+    std::vector<double> p0, p1, p2, arr_a, arr_b;
+    std::vector<int> csr_ptr, csr_col, outdeg_f, fol;
+    std::vector<int64_t> fol_ids;
+    std::vector<int64_t> sink_ids;   // sorted: the sink column -> sink id map
+    std::vector<int> csr_col_el;     // sink columns in edge-list order for every stream
+    std::vector<int> col_to_fol;     // sink column -> follower position or -1
+    // duplicate (source, sink) edges (a multigraph, opt_model.py:169-175 accepts them): the
+    // sweep's CSR row of a source holds its distinct sinks first (layer 0), then the 2nd
+    // occurrences (layer 1), ...; every layer has distinct sinks.  lay_end[lay_ptr[j] ..
+    // lay_ptr[j+1]) are the CSR ends of stream j's layers.  multi: some row has > 1 layer.
+    bool multi = false, ctrl_dup = false;
+    // two of the graph's own RealData times are equal -- among the wall sources
+    // (rd_ties), or with the controlled slot's replayed times too (rd_ties_ctrl, runs with
+    // an RQ_SRC_REALDATA controller): every replica meets that tie, so such runs go to the
+    // exact sequential sweep directly
+    bool rd_ties = false, rd_ties_ctrl = false;
+    std::vector<int> lay_ptr, lay_end;
+    // per-stream sink bitsets (32 sinks per word) for the K=1 bitset sweep, n_sinks <= 2048
+    int nw = 0;
+    std::vector<uint32_t> masks;
+    std::vector<uint32_t> fbits;   // follower set as a sink bitset (BL sweep)
+    // the controller posts before a wall event at the same time when that source is static
+    // or has a larger src_id (opt_model.py:279-281, :289-290): the sweeps' per-stream flag,
+    // in global memory for the GT instances (the others build it in LDS)
+    std::vector<int> cbf;
+    // controlled-slot arrays (PiecewiseConst / RealData controlled runs)
+    int ctrl_arr_off = 0, ctrl_arr_n = 0;
+};
+// validate the network and fill *g (rq_graph_build up to its uploads); RQ_OK or the
+// rq_status rq_graph_build returns for this description
+int topo_build(const rq_graph_desc* d, GraphTopo* g);
+
+// ---- the plan of one rq_run_batch call ----
+struct Plan {
+    int nK = 1, spl = 1, wpb = 4, n_sinks_pad = 0;
+    int64_t R = 0, chunk = 0, capsum = 0, cap_rows = 0;
+    int64_t rep_lo = 0, rep_cnt = 0;   // per-grid-point replica window (rq_batch_desc.rep_lo/rep_cnt)
+    std::vector<int> cap;
+    std::vector<int64_t> st_off;
+    std::vector<int> rd_k;   // stream -> per-replica RealData source k (rq_batch_desc.rd_*) or -1
+    // sequential (event log / max_events) sweep variant; K=1 sink-bitset variant
+    bool log = false, bits = false;
+    // K=1 on per-wave LDS sink bits for graphs past the bitset variant (> 64 sources)
+    bool bl = false;
+    size_t g_fb = 0, g_etab = 0, g_inv = 0, g_skip = 0;
+    bool g_inv_sh = false;   // general sweep: 1/c_j in the block's shared LDS (one grid point)
+    bool gs = false;         // LOG sweep: per-sink state in global memory, gs_slots wave slots
+    int64_t gs_slots = 0, gs_stride = 0;
+    // fused windowed sweep (n_str <= 64): arrivals generated in-kernel, window depth fw_h
+    bool fw = false;
+    int fw_h = 8, mstride = 1;
+    // general fast sweep on merged streams (rq_merge_streams; sweep_mode 6: the windowed
+    // per-source merge inside the sweep instead)
+    bool mrg = false;
+    // the sequential sweep over > RQ_MAX_STREAMS sources: it plays the merged sequence
+    // too (its own per-lane rings hold <= 32 sources per lane)
+    bool lmrg = false;
+    // merged streams with the per-stream tables (CSR starts, follower out-degrees, tie
+    // flags, 1/c_j) in global memory: graphs whose tables do not fit LDS (the GT instances;
+    // the sequential ones on merged streams always)
+    bool gt = false;
+    size_t off_mt = 0, off_mj = 0, off_mjh = 0, off_mlen = 0;
+    int64_t mrg_stride = 0;   // merged entries per replica (capacity)
+    int n_grp = 1;            // > RQ_MG_B sources: groups of the two-level merge
+    int grp_sz = RQ_MG_B;     //   streams per group (64 up to 64 groups: MergeArgs.grp_sz)
+    int64_t sub_stride = 0;   //   entries per (replica, group) of the first level
+    size_t off_sub_t = 0, off_sub_j = 0, off_sub_len = 0;
+    // the fused sweep's phases B / C on merged streams (rq_gen_streams + rq_merge_streams
+    // instead of in-kernel generation; sweep_mode 7: the in-kernel generating sweep)
+    bool fwm = false;
+    // fwm with the RedQueen controller: its Exp(1) draws by call pairs (SweepInst.pair;
+    // RQ_CTRL_DRAWS=0 keeps a Philox call per draw)
+    bool pair = false;
+    // fwm without event log or max_events: each wave integrates the rows of the replica it
+    // swept (SweepInst.scan), the chunk launches no rq_scan; RQ_SWEEP_SCAN=0 keeps the kernel
+    bool scan = false;
+    // general sweep LDS layout
+    int gwpb = 4, gwin = 16, gcol_lds = 1, gcol16 = 0;
+    size_t g_col = 0, g_ptr = 0, g_odf = 0, g_cbf = 0, g_wave = 0, g_wave_stride = 0, g_rank_off = 0,
+           g_win_off = 0, g_x_off = 0, g_total = 0, g_stage_off = 0;
+    size_t tables_bytes = 0;
+    // resident sweep waves per CU of the chosen instance (the persistent grid's slots)
+    int wpc = 0;
+    // pipelined chunks (merged-stream sweeps): nbuf buffer sets, chunk k on stream k % nbuf
+    // with set k % nbuf, so chunk k+1's generation / merge and chunk k-1's scan fill the
+    // wave slots chunk k's sweep tail leaves (rq_run_batch); off_set0 + set * set_stride
+    // is a set's base, the per-chunk offsets below are relative to it
+    int nbuf = 1;
+    bool order = false;   // longest-first replica order for the sweep (rq_order_replicas)
+    size_t off_set0 = 0, set_stride = 0, off_ord = 0;
+    size_t off_pwc = 0, off_pwmax = 0;
+    size_t off_invc = 0, off_streams = 0, off_slen = 0, off_rt = 0, off_rs = 0, off_rv = 0,
+           off_rc = 0, off_sall = 0, off_wq = 0, off_stoff = 0, off_cap = 0, off_rdk = 0, off_repidx = 0, off_gs = 0,
+           total = 0;
+};
+
+// The plan of batch b on graph g within `budget` bytes of workspace (<= 0: no budget); the
+// only device facts it uses are the three queries above.  RQ_OK or the rq_status the ABI
+// call returns.
+int make_plan(const GraphTopo& g, const rq_batch_desc* b, const Knobs& kn, double budget, Plan* p);
+// the instance a finished plan runs
+SweepInst sweep_inst(const Plan& p, int ctrl_kind);
+// the nine values of rq_plan_info_n (include/rq.h)
+void plan_info(const Plan& p, int ctrl_kind, int64_t info[9]);
+
+// ---- the controller's per-run tables ----
+struct CtrlTables {
+    std::vector<double> invc;         // [n_grid][n_str] 1 / c_j (RedQueen; else zeros)
+    std::vector<double> pwc, pwmax;   // OptPWSignificance: [n_grid][n_str][n_seg], [n_grid][n_str]
+};
+CtrlTables ctrl_tables(const GraphTopo& g, const rq_batch_desc* b);
+
+}  // namespace rqh

@@ -8,6 +8,7 @@
 #include <tuple>
 
 #include "../../include/rq.h"
+#include "rq_host.h"   // the planner's constants, SweepInst and the three device queries
 #include "rq_log_walk.h"
 
 // global replica id of position s of a call's replica space (rq_batch_desc.rep_lo /
@@ -56,8 +57,6 @@ __host__ __device__ __forceinline__ int64_t rq_replica_of(const GenArgs& a, int6
 {
     return a.rep_idx ? a.rep_idx[local] : rq_global_replica(a.rep0 + local, a.n_rep, a.rep_lo, a.rep_cnt);
 }
-
-#define RQ_MAX_STREAMS 2048   // 512 per fast instance (8 per lane); LOG instances 16 / 32 per lane
 
 struct SweepArgs {
     int64_t n_chunk, chunk0, n_rep, rep0;
@@ -173,11 +172,6 @@ struct MergeArgs {
     int grp_sz;
     unsigned long long* clk;   // RQ_PHASE_CLOCK builds only: per-phase s_memtime sums [8]
 };
-#define RQ_NPSUM1_LDS 516   // doubles of wave_npsum<1> scratch (== rq::npsum_lds_doubles<1>())
-// threads per block of the merged-stream sweep instances (1024: <= 128 VGPRs)
-#ifndef RQ_MRG_LB
-#define RQ_MRG_LB 1024
-#endif
 // wall events per branch-free batch of the merged-stream K = 1 sink-bit sweep: C5 sweep
 // per 4096 replicas on one stream (same box, round 5) 4: 139.0, 5: 136.1, 6: 135.0 ms;
 // the pipelined 8192-replica step 382.6 / 372.0 / 374.5 ms (gpurun_out/abc5)
@@ -189,7 +183,6 @@ struct MergeArgs {
 #ifndef RQ_MRG_BLB
 #define RQ_MRG_BLB 5
 #endif
-#define RQ_MG_B 512         // merge block: one source per thread (the fast general sweep: <= 512)
 
 struct ScanArgs {
     int64_t n_chunk, chunk0;
@@ -206,35 +199,9 @@ struct ScanArgs {
     int* wq;                // replica work queue (zeroed before the launch; null = one replica per wave)
 };
 
-// The sweep template instance a plan selects, one field per template axis.  rq_api.cpp
-// builds it from a Plan (sweep_inst: the planner's candidates, rq_plan_info and the
-// launch alike); each kernel file resolves it to the kernel in one place (sweep_kernel /
-// fw_kernel), which the launch and the occupancy query share.  The flags name the kernels'
-// template parameters (rq_kernels.hip, rq_sweep_fw.hip).
-struct SweepInst {
-    bool fused;   // rq_sweep_fw / rq_sweep_fwm (<= 64 sources), else the general rq_sweep
-    int nK;       // K variants (1..RQ_MAX_K)
-    bool col16;   // sink columns in LDS as uint16, else read from global memory as int
-    bool log;     // the sequential sweep (event log, max_events, duplicate edges, ties)
-    bool gs;      // log: the per-sink state in global memory (SweepArgs.gs)
-    bool bits;    // K = 1 on per-stream sink bitsets
-    bool bl;      // K = 1 on per-wave LDS sink bits (general sweep)
-    bool mrg;     // plays the merged streams of rq_merge_streams; else:
-    int spl;      //   general: sources per lane, 1 / 2 / 4 / 8 (log: 1 / 8 / 16 / 32)
-    int W;        //   fused: depth of the generated arrival rings, 32 / 16 / 8 (the general
-                  //   instances fix theirs: a window of 4; log: rings of 8, 4 at 32 per lane)
-    bool gt;      // mrg, general: the per-stream tables in global memory
-    bool pw;      // fused: the OptPWSignificance controller
-    bool pair;    // fused, mrg: the RedQueen controller's draws by call pairs (one Philox call per
-                  //   lane every other tile, both of its draws used), else a call per draw
-    bool scan;    // fused, mrg: the wave that swept a replica integrates its rows itself (rq_scan's
-                  //   sums, written to SweepArgs.metrics; no rq_scan launch for the chunk)
-};
-// SweepInst.scan: the per-wave LDS of the sweep's scan, aliased on the wave's sweep area
-// (dead after the tile loop, initialised again at the top of each replica); the layout of
-// rq::npsum_lds_doubles<nK + 2, RQ_FWS_NL>() -- 66 leaf slots, a block of 8192 rows has <= 65
-#define RQ_FWS_NL 66
-#define RQ_FWS_LDS_BYTES(nK) ((size_t)8 * (((nK) + 2 + 3) * RQ_FWS_NL + 4))
+// SweepInst (rq_host.h) names the sweep template instance a plan selects; the launches
+// below and the occupancy queries (rq_sweep_blocks_per_cu / rq_fw_blocks_per_cu, declared
+// there too) resolve it to the kernel in one place per kernel file.
 using SweepKernel = void (*)(SweepArgs);
 
 hipError_t rq_launch_gen(const GenArgs& a, hipStream_t s);
@@ -242,23 +209,15 @@ hipError_t rq_launch_gen(const GenArgs& a, hipStream_t s);
 // with merged streams, without uint16 columns or at W != 16)
 hipError_t rq_launch_sweep(const SweepArgs& a, const SweepInst& i, hipStream_t s);
 hipError_t rq_launch_scan(const ScanArgs& a, int nK, hipStream_t s);
-// blocks of 64 * wpb threads per CU the instance reaches with `lds` bytes of dynamic LDS
-// (rq_occupancy); <= 0: no instance or no device -- the planner takes the LDS bound
-int rq_sweep_blocks_per_cu(const SweepInst& i, int wpb, size_t lds);
 hipError_t rq_launch_merge(const MergeArgs& a, hipStream_t s);
 // > RQ_MG_B sources: level 1 over n_grp groups (a.n_str streams, grid C x n_grp), then
 // the second level over the groups' sequences (a.sub_*, a.n_grp "streams")
 hipError_t rq_launch_merge_groups(const MergeArgs& a, hipStream_t s);
 hipError_t rq_launch_merge_sub(const MergeArgs& a, hipStream_t s);
-// merged entries carry the stream as u16 (+ a u8 of its high bits past 65535 streams);
-// the two-level merge takes up to RQ_MG_B groups of RQ_MG_B streams
-#define RQ_MAX_STREAMS_MRG (RQ_MG_B * RQ_MG_B)
 // longest-first order of n <= 65536 replicas by len (descending; ties in any order)
 hipError_t rq_launch_order(const int* len, int64_t n, int* order, hipStream_t s);
-// the fused pair of rq_launch_sweep / rq_sweep_blocks_per_cu (SweepInst.fused)
+// the fused pair of rq_launch_sweep (SweepInst.fused)
 hipError_t rq_launch_sweep_fw(const SweepArgs& a, const SweepInst& i, hipStream_t s);
-int rq_fw_blocks_per_cu(const SweepInst& i, int wpb, size_t lds);
-int rq_cu_count();   // CUs of the current device (256 on MI355X when the query fails)
 
 // Blocks per CU a kernel reaches at `threads` threads and `lds` bytes of dynamic LDS
 // (the runtime's occupancy: VGPR, SGPR and LDS limits), cached per (kernel, threads,
