@@ -23,6 +23,9 @@
 // More than MG_CAP arrivals at ONE time (only replayed data can do that) cannot be
 // ordered in a round: the block emits them MG_CAP at a time and flags RQ_ST_TIE, which
 // sends the batch to the exact sequential sweep (engine.Graph.run(check=True)).
+//
+// 9-64 streams in one level go to rq_merge_flat below (the same output from windows in
+// which a lane holds an arrival, not a stream); <= 8 to the ranking merge rq_merge_rank.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cstdlib>
@@ -446,6 +449,256 @@ __global__ __launch_bounds__(MG_B) void rq_merge_streams(MergeArgs a)
     }
 }
 
+// ---------------------------------------------------------------------------
+// <= 64 streams in flat windows: the bucket rounds above give a lane a
+// stream, so a round's walk runs over (stream, cache slot) pairs that are mostly empty.
+// Here a block of FB threads merges a replica in windows of <= FCAP arrivals (two waves and
+// 1024 as launched: the smallest step of the shapes measured), and in every
+// pass over arrivals a lane slot holds an arrival:
+//
+//   run search: a stream is sorted, so its arrivals before the cut tau are a prefix of
+//   what is left of it.  FB / 64 lanes per stream find the prefix's end by comparison
+//   (an (FB / 64 + 1)-ary search from the cursor, one load per lane and step), so the
+//   window's total is known before LDS is touched: a window over FCAP is retried with
+//   half the span at the cost of the search alone;
+//   items: an exclusive scan of the run lengths numbers the window's arrivals
+//   0 .. nr - 1 in (stream, position) order; thread i, i + FB, ... finds its item's stream
+//   in the 64 prefix sums (6 LDS steps), loads its time (consecutive items of a run are
+//   consecutive addresses) and keeps time and key in registers across
+//   (a) the histogram of time sub-buckets, (b) the in-place scan of the counts and
+//   (c) the scatter into bucket order, where the bases serve as cursors and end as the
+//   buckets' ends; (d) ranks every entry inside its bucket by (t, stream, position) and
+//   writes it out, as the bucket rounds do.
+//
+// The output is the bucket rounds' element for element: every window emits all arrivals
+// before its cut in (t, stream, position in stream) order, whatever the cuts are.  More
+// than FCAP arrivals at ONE time are emitted FCAP at a time in (stream, position) order
+// and flagged, as there with MG_CAP.
+// ---------------------------------------------------------------------------
+// sub_of, kept inside the counts whatever the input (an unsorted stream's t < t_lo)
+template <int M>
+__device__ __forceinline__ int flat_sub(double t, double t_lo, double scale)
+{
+    const int sb = sub_of<M>(t, t_lo, scale);
+    return sb > 0 ? sb : 0;
+}
+
+template <int FB, int FCAP, int FT8>
+__global__ __launch_bounds__(FB) void rq_merge_flat(MergeArgs a)
+{
+    constexpr int FW = FB / 64;            // waves
+    constexpr int LPS = FB / 64;           // lanes per stream in the run search
+    constexpr int PT = FCAP / FB;          // items (and sub-buckets) per thread
+    constexpr int FM = FCAP;               // time sub-buckets per window
+    constexpr int FTARGET = FT8 * FCAP / 8;   // arrivals a window aims at
+    constexpr int KB = FCAP <= 1024 ? 10 : FCAP <= 2048 ? 11 : 12;   // bits of a position in a run
+    constexpr int SB_SH = KB + 6;          // kv = (sub-bucket << SB_SH) | (stream << KB) | position
+    static_assert(FCAP % FB == 0 && FCAP <= (1 << KB) && PT % 4 == 0 && SB_SH + KB <= 32, "packed fields");
+    __shared__ double st[FCAP];            // bucket order
+    __shared__ uint32_t sk[FCAP];          // (stream << KB) | position in the window's run
+    __shared__ __attribute__((aligned(16))) uint32_t cnt[FM];   // counts, then bases / cursors, then ends
+    __shared__ uint32_t pre[64];           // items before stream s in the window
+    __shared__ uint32_t sbase[64];         // stream s's cursor as an index into the replica's streams
+    __shared__ uint32_t wsum[2][FW], csum[FW];
+    __shared__ double wmin[FW];
+
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t rl = blockIdx.x;
+    const int s = tid / LPS, k = tid % LPS, g0l = lane & ~(LPS - 1);
+    const double* rep = a.streams + rl * a.capsum;
+    int L = 0;
+    uint32_t off = 0;
+    if (s < a.n_str) {
+        L = a.slen[(int64_t)s * a.slen_stride + rl];
+        off = (uint32_t)a.st_off[s];
+    }
+    int cur = 0;
+    double head = RQ_INF;
+    if (k == 0 && L > 0) head = rep[off];
+#pragma unroll
+    for (int q = 0; q < PT; ++q) cnt[tid + q * FB] = 0;
+    {
+        const double m = wave_min_f64(head);
+        const uint32_t sm = wave_sum_u32(k == 0 ? (uint32_t)L : 0u);
+        if (lane == 0) {
+            wmin[w] = m;
+            wsum[0][w] = sm;
+        }
+    }
+    __syncthreads();
+    double t_lo = wmin[0];
+    uint32_t total = 0;
+#pragma unroll
+    for (int q = 0; q < FW; ++q) {
+        t_lo = wmin[q] < t_lo ? wmin[q] : t_lo;
+        total += wsum[0][q];
+    }
+    double span = (a.end - t_lo) * ((double)FTARGET / (double)(total > 1 ? total : 1));
+    int64_t outpos = 0;
+    double* out_t = a.out_t + rl * a.mrg_stride;
+    uint16_t* out_j = a.out_j + rl * a.mrg_stride;
+    int status = 0;
+    int par = 1;   // wsum[par]: a retried window's sums are written while the last ones are read
+
+    while (t_lo <= a.end) {
+        double tau = t_lo + span;
+        if (!(tau > t_lo)) tau = next_up(t_lo);
+        // ---- the stream's run [cur, lo): its arrivals before tau ----
+        // invariant: entries below lo are before tau, entries from hi on are not
+        int lo = cur, hi = L;
+        for (;;) {
+            const int n = hi - lo;
+            const bool act = n > 0;
+            if (!__ballot(act)) break;
+            // probes lo + n (k + 1) / (LPS + 1) < hi, non-decreasing in k
+            const uint32_t un = (uint32_t)(act ? n : 0);
+            bool below = false;
+            if (act) below = rep[off + (uint32_t)lo + un * (uint32_t)(k + 1) / (uint32_t)(LPS + 1)] < tau;
+            const uint64_t bal = __ballot(below);
+            const uint32_t c = (uint32_t)__popc((uint32_t)(bal >> g0l) & ((1u << LPS) - 1u));   // a prefix of the probes
+            if (act) {
+                if (c < (uint32_t)LPS) hi = lo + (int)(un * (c + 1u) / (uint32_t)(LPS + 1));
+                if (c > 0) lo = lo + (int)(un * c / (uint32_t)(LPS + 1)) + 1;
+            }
+        }
+        const int ns = lo - cur;
+        const uint32_t incl = wave_scan_add(k == 0 ? (uint32_t)ns : 0u);
+        if (lane == 63) wsum[par][w] = incl;
+        __syncthreads();
+        uint32_t wo = 0, nr_all = 0;
+#pragma unroll
+        for (int q = 0; q < FW; ++q) {
+            const uint32_t v = wsum[par][q];
+            wo += q < w ? v : 0u;
+            nr_all += v;
+        }
+        par ^= 1;
+        uint32_t nr = nr_all;
+        if (nr_all > (uint32_t)FCAP) {
+            if (tau != next_up(t_lo)) {   // too many for one window: halve the cut (nothing to undo)
+                span = (tau - t_lo) * 0.5;
+                continue;
+            }
+            // more than FCAP arrivals at t_lo itself: the first FCAP in (stream, position)
+            // order (any subset of equal times is a time prefix), and flag the replica
+            nr = FCAP;
+            status |= a.strict_ties ? RQ_ST_UNORDERED : RQ_ST_TIE;
+        }
+        if (outpos + (int64_t)nr > a.mrg_stride) {   // past the merged capacity (uniform)
+            status |= RQ_ST_STREAM_OVERFLOW;
+            break;
+        }
+        if (nr == 0) break;   // (the head at t_lo is before tau: only unordered input gets here)
+        {
+            // the group's lanes hold the same incl - ns: the items before their stream
+            const uint32_t e0 = wo + incl - (uint32_t)ns;
+            const int room = e0 < nr ? (int)(nr - e0) : 0;
+            if (k == 0) {
+                pre[s] = e0;
+                sbase[s] = off + (uint32_t)cur;
+            }
+            cur += ns < room ? ns : room;
+            head = RQ_INF;
+            if (k == 0 && cur < L) head = rep[off + (uint32_t)cur];   // used after the scatter
+        }
+        __syncthreads();
+        // ---- the window's items into registers; (a) histogram ----
+        const double scale = (double)FM / (tau - t_lo);
+        double tv[PT];
+        uint32_t kv[PT];
+#pragma unroll
+        for (int q = 0; q < PT; ++q) {
+            // unconditional (a slot past the window repeats its last item and drops it below):
+            // the PT searches interleave, and no load waits behind a branch
+            const uint32_t i0 = (uint32_t)(tid + q * FB), i = i0 < nr ? i0 : nr - 1u;
+            uint32_t s2 = 0;   // the last stream with pre <= i (empty streams repeat a value)
+#pragma unroll
+            for (uint32_t step = 32; step > 0; step >>= 1) s2 += pre[s2 + step] <= i ? step : 0u;
+            const uint32_t pos = i - pre[s2];
+            tv[q] = rep[sbase[s2] + pos];
+            kv[q] = (s2 << KB) | pos;
+        }
+#pragma unroll
+        for (int q = 0; q < PT; ++q) {
+            if ((uint32_t)(tid + q * FB) < nr) {
+                const uint32_t sb = (uint32_t)flat_sub<FM>(tv[q], t_lo, scale);
+                atomicAdd(&cnt[sb], 1u);
+                kv[q] |= sb << SB_SH;
+            }
+        }
+        __syncthreads();
+        // ---- (b) bucket bases: exclusive scan of cnt in place (PT buckets per thread) ----
+        {
+            uint32_t v[PT], tsum = 0;
+#pragma unroll
+            for (int q = 0; q < PT; q += 4) {
+                const uint4 x = *reinterpret_cast<const uint4*>(&cnt[PT * tid + q]);
+                v[q] = x.x, v[q + 1] = x.y, v[q + 2] = x.z, v[q + 3] = x.w;
+                tsum += x.x + x.y + x.z + x.w;
+            }
+            const uint32_t ci = wave_scan_add(tsum);
+            if (lane == 63) csum[w] = ci;
+            __syncthreads();
+            uint32_t b = ci - tsum;
+#pragma unroll
+            for (int q = 0; q < FW; ++q) b += q < w ? csum[q] : 0u;
+#pragma unroll
+            for (int q = 0; q < PT; q += 4) {
+                uint4 x;
+                x.x = b, x.y = b + v[q], x.z = x.y + v[q + 1], x.w = x.z + v[q + 2];
+                b = x.w + v[q + 3];
+                *reinterpret_cast<uint4*>(&cnt[PT * tid + q]) = x;
+            }
+        }
+        __syncthreads();
+        // ---- (c) into bucket order: a bucket's base is its cursor, and ends as its end ----
+#pragma unroll
+        for (int q = 0; q < PT; ++q) {
+            if ((uint32_t)(tid + q * FB) < nr) {
+                const uint32_t pos = atomicAdd(&cnt[kv[q] >> SB_SH], 1u);
+                st[pos] = tv[q];
+                sk[pos] = kv[q] & ((1u << SB_SH) - 1u);
+            }
+        }
+        {
+            const double m = wave_min_f64(head);
+            if (lane == 0) wmin[w] = m;
+        }
+        __syncthreads();
+        // ---- (d) rank inside the bucket, written out in play order ----
+        for (int i = tid; i < (int)nr; i += FB) {
+            const double x = st[i];
+            const uint32_t kx = sk[i];
+            const int sb = flat_sub<FM>(x, t_lo, scale);
+            const int g0 = sb > 0 ? (int)cnt[sb - 1] : 0, g1 = (int)cnt[sb];
+            int r = 0;
+            for (int q = g0; q < g1; ++q) {
+                const double y = st[q];
+                r += (y < x || (y == x && sk[q] < kx)) ? 1 : 0;
+            }
+            // streaming stores, as the bucket rounds': the output must not evict the input
+            __builtin_nontemporal_store(x, &out_t[outpos + g0 + r]);
+            __builtin_nontemporal_store((uint16_t)(kx >> KB), &out_j[outpos + g0 + r]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < PT; ++q) cnt[tid + q * FB] = 0;   // the next histogram is two barriers away
+        double t_next = wmin[0];
+#pragma unroll
+        for (int q = 1; q < FW; ++q) t_next = wmin[q] < t_next ? wmin[q] : t_next;
+        outpos += nr;
+        // next cut: aim at FTARGET arrivals, grow at most 4x per window
+        const double wdt = tau - t_lo;
+        const double f = (double)FTARGET / (double)(nr > 64 ? nr : 64);
+        span = wdt * (f < 4.0 ? f : 4.0);
+        t_lo = t_next;   // the heads after the window (an equal-time window: t_lo again)
+    }
+    if (tid == 0) {
+        a.out_len[rl] = (int)outpos;
+        if (status) atomicOr(&a.status[a.chunk0 + rl], status);
+    }
+}
+
 // A handful of streams (C4 / C2: the README graph's three, ~2100 arrivals per replica):
 // the bucket rounds ran a 64-lane block with 3 lanes walking, so here the merge is a
 // RANKING instead.  A block stages its replica's streams in LDS (coalesced), then every
@@ -522,6 +775,36 @@ hipError_t rq_launch_merge(const MergeArgs& a, hipStream_t s)
             hipLaunchKernelGGL((rq_merge_rank<4>), dim3((unsigned)a.n_chunk), dim3(256), lds, s, a);
         else
             hipLaunchKernelGGL((rq_merge_rank<8>), dim3((unsigned)a.n_chunk), dim3(256), lds, s, a);
+        return hipGetLastError();
+    }
+    // <= 64 streams: flat windows, unless the ranking merge was switched off (RQ_MERGE_SMALL=0
+    // means the bucket rounds, whose own tests set it) or RQ_MERGE_FLAT=0 (A/B and tests)
+    const char* ef = getenv("RQ_MERGE_FLAT");
+    const int flat = ef ? atoi(ef) : 1;
+    if (small_on && flat != 0 && a.n_str <= 64 && a.capsum < ((int64_t)1 << 31)) {
+#define RQ_FLAT_LAUNCH(FB, FCAP, FT8) \
+    hipLaunchKernelGGL((rq_merge_flat<FB, FCAP, FT8>), dim3((unsigned)a.n_chunk), dim3(FB), 0, s, a)
+#ifdef RQ_FLAT_SHAPES
+        // tuning builds (EXTRA=-DRQ_FLAT_SHAPES): RQ_MERGE_FLAT = waves * 100000 + window
+        // capacity * 10 + eighths of it a window aims at (DESIGN 22 has the measurements)
+        switch (flat) {
+        case 102566: RQ_FLAT_LAUNCH(64, 256, 6); return hipGetLastError();
+        case 105126: RQ_FLAT_LAUNCH(64, 512, 6); return hipGetLastError();
+        case 205126: RQ_FLAT_LAUNCH(128, 512, 6); return hipGetLastError();
+        case 210245: RQ_FLAT_LAUNCH(128, 1024, 5); return hipGetLastError();
+        case 210246: RQ_FLAT_LAUNCH(128, 1024, 6); return hipGetLastError();
+        case 215366: RQ_FLAT_LAUNCH(128, 1536, 6); return hipGetLastError();
+        case 220486: RQ_FLAT_LAUNCH(128, 2048, 6); return hipGetLastError();
+        case 410246: RQ_FLAT_LAUNCH(256, 1024, 6); return hipGetLastError();
+        case 410247: RQ_FLAT_LAUNCH(256, 1024, 7); return hipGetLastError();
+        case 420486: RQ_FLAT_LAUNCH(256, 2048, 6); return hipGetLastError();
+        case 430726: RQ_FLAT_LAUNCH(256, 3072, 6); return hipGetLastError();
+        case 820486: RQ_FLAT_LAUNCH(512, 2048, 6); return hipGetLastError();
+        default: break;
+        }
+#endif
+        RQ_FLAT_LAUNCH(128, 1024, 7);
+#undef RQ_FLAT_LAUNCH
         return hipGetLastError();
     }
     if (a.n_str <= 64)
