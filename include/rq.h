@@ -39,6 +39,7 @@
  *   rq_log_followers    utils.rank_of_src_in_df + the same integrals per sink column
  *                       and int_r_2_true                     utils.py:38-56, :84-128
  *                       for every replica of an RQ_RUN_EVENT_LOG batch at once
+ *   rq_log_followers_tiled  the same, sink-tiled: graphs of up to 40,960 sinks
  *   rq_log_rank_hist    utils.rank_of_src_in_df + time_in_top_k for every K at once:
  *                       the seen sink-time per rank value and time bin
  *                       utils.py:38-56, :84-98 (opt_runs.py:31-33's Ks curve)
@@ -474,6 +475,46 @@ int rq_log_followers(rq_graph_t g, const double* ev_t, const int32_t* ev_src,
                      int32_t* status,      /* device [n_rep] */
                      void* hip_stream);
 int32_t rq_log_followers_max_sinks(int32_t nK, int32_t with_rows);   /* 0 for a bad nK */
+
+/* rq_log_followers past its sink limit: the same outputs -- shapes, layout, meaning and bits
+ * -- for a graph of 1 <= n_sinks <= RQ_FOLLOWERS_TILED_MAX_SINKS sinks.  The sink columns are
+ * cut into tiles of rq_log_followers_tile_sinks() columns (tile i owns columns [i TS,
+ * min((i + 1) TS, n_sinks)); a graph of at most TS sinks is one tile).  One wavefront per
+ * (replica, tile) replays the replica's whole log against a CSR of the tile's edges and
+ * keeps the state of its own sinks in LDS; a second kernel, one wavefront per replica with
+ * every sink's rank in LDS (4 bytes a sink: 40,960 sinks fill one workgroup's 160 KiB),
+ * gives r2_true and status and overwrites vals with NaN for a TIE / EMPTY replica.  Both
+ * are enqueued in order on hip_stream.
+ *   Exactness: a sink's sums see only that sink's rows, in time order from 0.0 under
+ * rq_log_followers' rule, so vals, first_t and rows do not depend on the tiling; r2_true is
+ * rq_log_followers' loop over the whole graph.  Every finite output equals
+ * rq_log_followers' bit for bit where both entries run, NaN where it has NaN, integers
+ * equal; no replica's output depends on its neighbours or on the launch.  Every element is
+ * written once, but for vals of a TIE / EMPTY replica (the tile's value, then NaN, in
+ * stream order).
+ *   workspace: device, rq_log_followers_tiled_workspace bytes = one int32 flag per
+ * (replica, tile), 4 n_rep ceil(n_sinks / TS) rounded up to 256; contents on entry do not
+ * matter, no zeroing is needed.  Enqueues on hip_stream only: no allocation, no
+ * synchronisation.
+ *   RQ_EINVAL, before any HIP call: rq_log_followers' cases, a null workspace or one smaller
+ * than the query's size, n_rep * tiles > INT32_MAX.  RQ_EUNSUPPORTED: a graph with
+ * duplicate edges, or with more than RQ_FOLLOWERS_TILED_MAX_SINKS sinks -- above that
+ * int_r_2_true would need the ranks of a replica outside LDS, which is not built.  A refused
+ * call launches nothing.
+ *   Added without an ABI version change (RQ_ABI_VERSION stays 6); a caller detects the
+ * functions by their symbols. */
+#define RQ_FOLLOWERS_TILED_MAX_SINKS 40960   /* the r2 pass: 4 B per sink in 160 KiB */
+int32_t rq_log_followers_tile_sinks(void);   /* TS */
+int rq_log_followers_tiled_workspace(rq_graph_t g, int64_t n_rep, size_t* bytes);
+int rq_log_followers_tiled(rq_graph_t g, const double* ev_t, const int32_t* ev_src,
+                           const int64_t* counts, int64_t n_rep, int64_t ev_cap,
+                           const int32_t* Ks, int32_t nK,  /* host, 1 <= nK <= 4, K >= 1 */
+                           double* vals,         /* device [n_rep][n_sinks][nK + 2] */
+                           double* first_t,      /* device [n_rep][n_sinks] */
+                           int32_t* rows,        /* device [n_rep][n_sinks][2]: own, wall; or NULL */
+                           double* r2_true,      /* device [n_rep] */
+                           int32_t* status,      /* device [n_rep] */
+                           void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /* The rank distribution of a batch's event logs: the third axis of rank_of_src_in_df's
  * pivot table (utils.py:38-56), the rank value itself -- per time bin, how long the seen

@@ -67,6 +67,7 @@ REPLAY_CHUNK_ROWS = 4096   # RC_L: rows per workgroup of the chunked replay
 MAX_K = 4
 MAX_RD = 64
 TIMELINE_MAX_SINKS = 12288   # RQ_TIMELINE_MAX_SINKS
+FOLLOWERS_TILED_MAX_SINKS = 40960   # RQ_FOLLOWERS_TILED_MAX_SINKS
 RANK_HIST_MAX_RANKS = 255    # RQ_RANK_HIST_MAX_RANKS
 
 _P = C.c_void_p
@@ -160,6 +161,11 @@ def lib():
     L.rq_log_followers.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int64, _pi32, C.c_int32, _P, _P,
                                    _P, _P, _P, _P]
     L.rq_log_followers_max_sinks.argtypes = [C.c_int32, C.c_int32]
+    L.rq_log_followers_tile_sinks.argtypes = []
+    L.rq_log_followers_tile_sinks.restype = C.c_int32
+    L.rq_log_followers_tiled_workspace.argtypes = [_P, C.c_int64, C.POINTER(C.c_size_t)]
+    L.rq_log_followers_tiled.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int64, _pi32, C.c_int32, _P, _P,
+                                         _P, _P, _P, _P, C.c_size_t, _P]
     L.rq_log_rank_hist.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int32,
                                    _P, _P, _P, _P, _P]
     L.rq_log_followers_max_sinks.restype = C.c_int32
@@ -170,7 +176,8 @@ def lib():
                "rq_replay_workspace_size", "rq_metrics_replay", "rq_metrics_replay_batch",
                "rq_oracle_workspace_size",
                "rq_oracle_dp", "rq_rank_table", "rq_u_int", "rq_log_rows", "rq_log_expand",
-               "rq_log_timeline", "rq_log_followers", "rq_log_rank_hist"):
+               "rq_log_timeline", "rq_log_followers", "rq_log_followers_tiled_workspace",
+               "rq_log_followers_tiled", "rq_log_rank_hist"):
         getattr(L, fn).restype = C.c_int
     if L.rq_abi_version() != ABI_VERSION:
         raise ImportError("librq.so ABI version mismatch")
@@ -217,4 +224,6 @@ EXPORTED = ["rq_abi_version", "rq_strerror", "rq_graph_build", "rq_graph_free", 
             "rq_event_capacity", "rq_plan_info", "rq_plan_info_n", "rq_run_batch", "rq_replay_workspace_size",
             "rq_metrics_replay", "rq_metrics_replay_batch", "rq_oracle_workspace_size", "rq_oracle_dp", "rq_rank_table",
             "rq_u_int", "rq_log_rows", "rq_log_expand", "rq_log_timeline", "rq_log_followers",
-            "rq_log_rank_hist", "rq_timing", "rq_timing_read"]   # rq_log_followers_max_sinks returns int32_t, no status
+            "rq_log_followers_tiled_workspace", "rq_log_followers_tiled",
+            "rq_log_rank_hist", "rq_timing", "rq_timing_read"]
+# rq_log_followers_max_sinks and rq_log_followers_tile_sinks return int32_t, no status

@@ -248,17 +248,18 @@ def timeline_frame(edges, Ks, metrics, posts, status):
 
 
 def run_followers(sim_opts, seeds=range(10), Ks=(1,), ctrl="opt", randomize=True,
-                  chunk_replicas=None, **run_kw):
+                  chunk_replicas=None, tiled=None, **run_kw):
     """The ensemble's metrics per follower: one row per sink with ``sink_id`` and, for every
     metric (top_K..., rank_int, rank_sq_int: the integrals over the sink's seen span) and
     for its own / wall rows, the mean and the standard error over the replicas, plus ``n``
     (replicas averaged) and ``n_flagged`` (TIE / EMPTY replicas, left out).  Seeds, chunks
     and ``run_kw`` as in run_timeline: every chunk's per-sink values are gathered on the
-    host and reduced in seed order, so the frame does not depend on the chunking."""
+    host and reduced in seed order, so the frame does not depend on the chunking.  ``tiled``
+    goes to BatchResult.followers (None: the sink-tiled kernel past the plain one's limit)."""
     val, rws, sts = [], [], []
     fl = None
     for res in _seed_chunks(sim_opts, seeds, Ks, ctrl, randomize, chunk_replicas, run_kw, "run_followers"):
-        fl = res.followers(Ks=Ks, rows=True)
+        fl = res.followers(Ks=Ks, rows=True, tiled=tiled)
         val.append(fl.vals.cpu().numpy())
         rws.append(fl.rows.cpu().numpy())
         sts.append(fl.status.cpu().numpy())

@@ -171,6 +171,7 @@ struct Stage {
 struct rq_graph : GraphTopo {
     DevBuf<int64_t> d_sink_ids, d_src_id;
     DevBuf<int> d_csr_col_el, d_lay_ptr, d_lay_end;
+    DevBuf<int> d_tile_ptr, d_tile_col;   // the sink-tiled CSR (n_tiles > 0)
     DevBuf<uint32_t> d_mask, d_fbits;
     DevBuf<int> d_kind, d_orig, d_arr_off, d_arr_n, d_csr_ptr, d_csr_col, d_outdeg_f, d_fol, d_cbf;
     DevBuf<uint32_t> d_seed;
@@ -208,6 +209,8 @@ int rq_graph::upload()
         (rc = d_csr_col_el.upload(csr_col_el)) || (rc = d_cbf.upload(cbf)))
         return rc;
     if (multi && ((rc = d_lay_ptr.upload(lay_ptr)) || (rc = d_lay_end.upload(lay_end))))
+        return rc;
+    if (n_tiles > 0 && ((rc = d_tile_ptr.upload(tile_ptr)) || (rc = d_tile_col.upload(tile_col))))
         return rc;
     return RQ_OK;
 }
@@ -1136,6 +1139,47 @@ int rq_log_followers(rq_graph_t g, const double* ev_t, const int32_t* ev_src, co
     hipStream_t st = (hipStream_t)hip_stream;
     TimedLaunch tl(K_REPLAY, st);
     return rq_launch_followers(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
+}
+
+int32_t rq_log_followers_tile_sinks(void) { return RQ_FOLLOWERS_TILE_SINKS; }
+
+int rq_log_followers_tiled_workspace(rq_graph_t g, int64_t n_rep, size_t* bytes)
+{
+    if (!g || !bytes || n_rep < 1 || n_rep > INT32_MAX) return RQ_EINVAL;
+    if (log_unsupported(g, RQ_FOLLOWERS_TILED_MAX_SINKS)) return RQ_EUNSUPPORTED;
+    *bytes = rqh::followers_tiled_ws_bytes(g->n_sinks, n_rep);
+    return RQ_OK;
+}
+
+int rq_log_followers_tiled(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const int64_t* counts,
+                           int64_t n_rep, int64_t ev_cap, const int32_t* Ks, int32_t nK, double* vals,
+                           double* first_t, int32_t* rows, double* r2_true, int32_t* status, void* workspace,
+                           size_t workspace_bytes, void* hip_stream)
+{
+    if (!g || !ev_t || !ev_src || !counts || !vals || !first_t || !r2_true || !status) return RQ_EINVAL;
+    // ev_cap <= 2^24: as rq_log_followers
+    if (n_rep < 1 || n_rep > INT32_MAX || ev_cap < 1 || ev_cap > (1 << 24)) return RQ_EINVAL;
+    FollowersTiledArgs a{};
+    if (!copy_ks(Ks, nK, a.f.Ks)) return RQ_EINVAL;
+    if (!workspace) return RQ_EINVAL;
+    if (log_unsupported(g, RQ_FOLLOWERS_TILED_MAX_SINKS)) return RQ_EUNSUPPORTED;
+    // one block per (replica, tile) on the grid's x axis
+    if (n_rep * (int64_t)g->n_tiles > INT32_MAX) return RQ_EINVAL;
+    if (workspace_bytes < rqh::followers_tiled_ws_bytes(g->n_sinks, n_rep)) return RQ_EINVAL;
+    a.f.log = log_view(g, ev_t, ev_src, counts, n_rep, ev_cap);
+    a.f.nK = nK;
+    a.f.vals = vals;
+    a.f.first_t = first_t;
+    a.f.rows = rows;
+    a.f.r2_true = r2_true;
+    a.f.status = status;
+    a.tile_ptr = g->d_tile_ptr.p;
+    a.tile_col = g->d_tile_col.p;
+    a.n_tiles = g->n_tiles;
+    a.flags = static_cast<int32_t*>(workspace);
+    hipStream_t st = (hipStream_t)hip_stream;
+    TimedLaunch tl(K_REPLAY, st);
+    return rq_launch_followers_tiled(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
 }
 
 int rq_log_rank_hist(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const int64_t* counts,

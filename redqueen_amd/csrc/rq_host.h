@@ -53,6 +53,17 @@ struct SweepInst {
 #define RQ_FWS_NL 66
 #define RQ_FWS_LDS_BYTES(nK) ((size_t)8 * (((nK) + 2 + 3) * RQ_FWS_NL + 4))
 
+// The sink-tiled follower kernels (rq_followers_tiled.hip): sink columns per tile.  A tile's
+// per-sink state -- 12 + 8 (nK + 2) bytes, 8 more with row counts -- lives in one workgroup's
+// 160 KiB of LDS whatever nK and the counts, so TS <= 2409; 2048 is the measured choice
+// (-DRQ_FOLLOWERS_TILE_SINKS=... builds the other for the A/B).
+#ifndef RQ_FOLLOWERS_TILE_SINKS
+#define RQ_FOLLOWERS_TILE_SINKS 2048
+#endif
+static_assert(RQ_FOLLOWERS_TILE_SINKS >= 1 &&
+                  (long long)RQ_FOLLOWERS_TILE_SINKS * (12 + 8 * (RQ_MAX_K + 2) + 8) <= 160 * 1024,
+              "a tile of every nK / rows variant must fit one workgroup's LDS");
+
 // ---- the planner's three questions to the device ----
 // Defined next to the kernels (the rq_kernels and rq_sweep_fw files); a program that links the
 // host core without them supplies its own.
@@ -66,6 +77,14 @@ int rq_cu_count();   // CUs of the current device (256 on MI355X when the query 
 namespace rqh {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// sink tiles of a graph of n_sinks sinks, and the workspace of rq_log_followers_tiled on it:
+// one int32 flag per (replica, tile), rounded up to 256 bytes
+inline int followers_tiles(int n_sinks) { return (n_sinks + RQ_FOLLOWERS_TILE_SINKS - 1) / RQ_FOLLOWERS_TILE_SINKS; }
+inline size_t followers_tiled_ws_bytes(int n_sinks, int64_t n_rep)
+{
+    return align_up((size_t)4 * (size_t)n_rep * (size_t)followers_tiles(n_sinks), 256);
+}
 
 // ---- environment knobs ----
 // Everything a plan or a launch depends on besides its arguments.  read_knobs() reads the
@@ -176,6 +195,14 @@ struct GraphTopo {
     // or has a larger src_id (opt_model.py:279-281, :289-290): the sweeps' per-stream flag,
     // in global memory for the GT instances (the others build it in LDS)
     std::vector<int> cbf;
+    // the CSR cut into sink tiles of RQ_FOLLOWERS_TILE_SINKS columns (tile i owns columns
+    // [i TS, min((i + 1) TS, n_sinks))), for graphs without duplicate edges and with at most
+    // RQ_FOLLOWERS_TILED_MAX_SINKS sinks (n_tiles == 0 otherwise): tile_ptr[n_tiles][n_str + 1]
+    // indexes tile_col[n_edges], laid out tile-major, and stream j's entry of tile i is the
+    // columns of j's row that fall in the tile (global column indices, the row's order).  So
+    // csr_ptr = tile_ptr + i (n_str + 1), csr_col = tile_col is a CSR of the tile's edges.
+    int n_tiles = 0;
+    std::vector<int> tile_ptr, tile_col;
     // controlled-slot arrays (PiecewiseConst / RealData controlled runs)
     int ctrl_arr_off = 0, ctrl_arr_n = 0;
 };

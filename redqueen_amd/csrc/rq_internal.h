@@ -412,6 +412,16 @@ struct FollowersArgs {
 };
 hipError_t rq_launch_followers(const FollowersArgs& a, hipStream_t s);
 
+// ---- the same past the LDS sink limit: sink tiles + an r2 pass (rq_followers_tiled.hip) ----
+struct FollowersTiledArgs {
+    FollowersArgs f;          // f.log: the graph's full CSR (the r2 pass)
+    const int* tile_ptr;      // [n_tiles][n_str + 1] into tile_col (GraphTopo)
+    const int* tile_col;      // [n_edges]
+    int n_tiles;
+    int32_t* flags;           // [n_rep][n_tiles] workspace; bit 0: a sink of the tile got two rows at one t
+};
+hipError_t rq_launch_followers_tiled(const FollowersTiledArgs& a, hipStream_t s);
+
 // ---- rank distribution from event logs (rq_rank_hist.hip) ----
 struct RankHistArgs {
     LogView log;

@@ -212,6 +212,35 @@ int topo_build(const rq_graph_desc* d, GraphTopo* g)
     for (int c : g->fol) g->fbits[c / 32] |= 1u << (c % 32);
     g->cbf.resize(g->n_str);
     for (int j = 0; j < g->n_str; ++j) g->cbf[j] = g->is_static[j] || g->ctrl_src_id < g->src_id[j];
+
+    // the sink-tiled CSR (rq_host.h): a stable counting sort of the edges by (tile, stream)
+    if (!g->multi && g->n_sinks <= RQ_FOLLOWERS_TILED_MAX_SINKS) {
+        const int TS = RQ_FOLLOWERS_TILE_SINKS;
+        const int nt = followers_tiles(g->n_sinks);
+        const size_t stride = (size_t)g->n_str + 1;
+        g->n_tiles = nt;
+        g->tile_ptr.assign((size_t)nt * stride, 0);
+        g->tile_col.resize(g->csr_col_el.size());
+        std::vector<int> at((size_t)nt * g->n_str, 0);   // counts, then write cursors
+        for (int j = 0; j < g->n_str; ++j)
+            for (int e = g->csr_ptr[j]; e < g->csr_ptr[j + 1]; ++e)
+                ++at[(size_t)(g->csr_col_el[e] / TS) * g->n_str + j];
+        int off = 0;
+        for (int i = 0; i < nt; ++i) {
+            for (int j = 0; j < g->n_str; ++j) {
+                g->tile_ptr[i * stride + j] = off;
+                const int n = at[(size_t)i * g->n_str + j];
+                at[(size_t)i * g->n_str + j] = off;
+                off += n;
+            }
+            g->tile_ptr[i * stride + g->n_str] = off;
+        }
+        for (int j = 0; j < g->n_str; ++j)
+            for (int e = g->csr_ptr[j]; e < g->csr_ptr[j + 1]; ++e) {
+                const int c = g->csr_col_el[e];
+                g->tile_col[at[(size_t)(c / TS) * g->n_str + j]++] = c;
+            }
+    }
     return RQ_OK;
 }
 

@@ -784,27 +784,47 @@ class BatchResult:
         return Timeline(e, ed, [int(k) for k in ks], metrics, posts, status, wp,
                         np.sort(g.sink_ids))
 
-    def followers(self, Ks=None, rows=False, stream=None):
+    def followers(self, Ks=None, rows=False, stream=None, tiled=None):
         """The metrics split over the followers, straight from the event logs
         (rq_log_followers): per (replica, sink) the integrals of I(r <= K-1), r and r^2
         over the sink's seen span, its first-row time and, with ``rows``, its own / wall
-        row counts; per replica int_r_2_true.  ``Ks``: default the result's own.  Returns
-        a ``Followers`` of device tensors; needs event_log=True."""
+        row counts; per replica int_r_2_true.  ``Ks``: default the result's own.
+        ``tiled``: None takes rq_log_followers while the graph's sinks fit its limit
+        (rq_log_followers_max_sinks) and the sink-tiled rq_log_followers_tiled (up to
+        FOLLOWERS_TILED_MAX_SINKS sinks, the same bits) past it; True / False force the
+        tiled / the plain entry.  Returns a ``Followers`` of device tensors; needs
+        event_log=True."""
         g = self._log_graph()
         ks = self._log_ks(Ks)
+        lib = L.lib()
+        if tiled is None:
+            tiled = g.n_sinks > lib.rq_log_followers_max_sinks(ks.size, 1 if rows else 0)
         use = stream or torch.cuda.current_stream()
         with torch.cuda.stream(use):
             dev = self.ev_t.device
             R, cap = self.ev_t.shape
+            ws = None
+            if tiled:   # refused graphs are refused before anything is allocated
+                nb = C.c_size_t()
+                L.check("rq_log_followers_tiled_workspace",
+                        lib.rq_log_followers_tiled_workspace(g._h, R, C.byref(nb)))
+                ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
             vals = torch.empty((R, g.n_sinks, ks.size + 2), dtype=torch.float64, device=dev)
             first_t = torch.empty((R, g.n_sinks), dtype=torch.float64, device=dev)
             rw = torch.empty((R, g.n_sinks, 2), dtype=torch.int32, device=dev) if rows else None
             r2 = torch.empty(R, dtype=torch.float64, device=dev)
             status = torch.empty(R, dtype=torch.int32, device=dev)
-            L.check("rq_log_followers", L.lib().rq_log_followers(
-                g._h, self.ev_t.data_ptr(), self.ev_src.data_ptr(), self.counts.data_ptr(), R, cap,
-                ks.ctypes.data_as(L._pi32), ks.size, vals.data_ptr(), first_t.data_ptr(),
-                rw.data_ptr() if rows else None, r2.data_ptr(), status.data_ptr(), use.cuda_stream))
+            if tiled:
+                L.check("rq_log_followers_tiled", lib.rq_log_followers_tiled(
+                    g._h, self.ev_t.data_ptr(), self.ev_src.data_ptr(), self.counts.data_ptr(), R, cap,
+                    ks.ctypes.data_as(L._pi32), ks.size, vals.data_ptr(), first_t.data_ptr(),
+                    rw.data_ptr() if rows else None, r2.data_ptr(), status.data_ptr(),
+                    ws.data_ptr(), nb.value, use.cuda_stream))   # ws: allocated on `use`, reused there only
+            else:
+                L.check("rq_log_followers", lib.rq_log_followers(
+                    g._h, self.ev_t.data_ptr(), self.ev_src.data_ptr(), self.counts.data_ptr(), R, cap,
+                    ks.ctypes.data_as(L._pi32), ks.size, vals.data_ptr(), first_t.data_ptr(),
+                    rw.data_ptr() if rows else None, r2.data_ptr(), status.data_ptr(), use.cuda_stream))
         return Followers([int(k) for k in ks], vals, first_t, rw, r2, status, np.sort(g.sink_ids))
 
     def rank_hist(self, ranks=64, edges=None, bins=None, stream=None):
