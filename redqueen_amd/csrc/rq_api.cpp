@@ -1119,16 +1119,16 @@ int32_t rq_log_followers_max_sinks(int32_t nK, int32_t with_rows)
     return RQ_FOLLOWERS_LDS_BYTES / rq_followers_sink_bytes(nK, with_rows != 0);
 }
 
-int rq_log_followers(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const int64_t* counts,
-                     int64_t n_rep, int64_t ev_cap, const int32_t* Ks, int32_t nK, double* vals,
-                     double* first_t, int32_t* rows, double* r2_true, int32_t* status, void* hip_stream)
+// What rq_log_followers and rq_log_followers_tiled check first and hand to their kernels;
+// each goes on with its own sink limit.
+static int followers_args(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const int64_t* counts,
+                          int64_t n_rep, int64_t ev_cap, const int32_t* Ks, int32_t nK, double* vals,
+                          double* first_t, int32_t* rows, double* r2_true, int32_t* status, FollowersArgs& a)
 {
     if (!g || !ev_t || !ev_src || !counts || !vals || !first_t || !r2_true || !status) return RQ_EINVAL;
     // ev_cap <= 2^24 bounds every rank, so rank^2 < 2^48 and the replica's sum stays in int64
     if (n_rep < 1 || n_rep > INT32_MAX || ev_cap < 1 || ev_cap > (1 << 24)) return RQ_EINVAL;
-    FollowersArgs a{};
     if (!copy_ks(Ks, nK, a.Ks)) return RQ_EINVAL;
-    if (log_unsupported(g, rq_log_followers_max_sinks(nK, rows != nullptr))) return RQ_EUNSUPPORTED;
     a.log = log_view(g, ev_t, ev_src, counts, n_rep, ev_cap);
     a.nK = nK;
     a.vals = vals;
@@ -1136,6 +1136,18 @@ int rq_log_followers(rq_graph_t g, const double* ev_t, const int32_t* ev_src, co
     a.rows = rows;
     a.r2_true = r2_true;
     a.status = status;
+    return RQ_OK;
+}
+
+int rq_log_followers(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const int64_t* counts,
+                     int64_t n_rep, int64_t ev_cap, const int32_t* Ks, int32_t nK, double* vals,
+                     double* first_t, int32_t* rows, double* r2_true, int32_t* status, void* hip_stream)
+{
+    FollowersArgs a{};
+    const int rc = followers_args(g, ev_t, ev_src, counts, n_rep, ev_cap, Ks, nK, vals, first_t, rows, r2_true,
+                                  status, a);
+    if (rc != RQ_OK) return rc;
+    if (log_unsupported(g, rq_log_followers_max_sinks(nK, rows != nullptr))) return RQ_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)hip_stream;
     TimedLaunch tl(K_REPLAY, st);
     return rq_launch_followers(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
@@ -1156,23 +1168,15 @@ int rq_log_followers_tiled(rq_graph_t g, const double* ev_t, const int32_t* ev_s
                            double* first_t, int32_t* rows, double* r2_true, int32_t* status, void* workspace,
                            size_t workspace_bytes, void* hip_stream)
 {
-    if (!g || !ev_t || !ev_src || !counts || !vals || !first_t || !r2_true || !status) return RQ_EINVAL;
-    // ev_cap <= 2^24: as rq_log_followers
-    if (n_rep < 1 || n_rep > INT32_MAX || ev_cap < 1 || ev_cap > (1 << 24)) return RQ_EINVAL;
     FollowersTiledArgs a{};
-    if (!copy_ks(Ks, nK, a.f.Ks)) return RQ_EINVAL;
+    const int rc = followers_args(g, ev_t, ev_src, counts, n_rep, ev_cap, Ks, nK, vals, first_t, rows, r2_true,
+                                  status, a.f);
+    if (rc != RQ_OK) return rc;
     if (!workspace) return RQ_EINVAL;
     if (log_unsupported(g, RQ_FOLLOWERS_TILED_MAX_SINKS)) return RQ_EUNSUPPORTED;
     // one block per (replica, tile) on the grid's x axis
     if (n_rep * (int64_t)g->n_tiles > INT32_MAX) return RQ_EINVAL;
     if (workspace_bytes < rqh::followers_tiled_ws_bytes(g->n_sinks, n_rep)) return RQ_EINVAL;
-    a.f.log = log_view(g, ev_t, ev_src, counts, n_rep, ev_cap);
-    a.f.nK = nK;
-    a.f.vals = vals;
-    a.f.first_t = first_t;
-    a.f.rows = rows;
-    a.f.r2_true = r2_true;
-    a.f.status = status;
     a.tile_ptr = g->d_tile_ptr.p;
     a.tile_col = g->d_tile_col.p;
     a.n_tiles = g->n_tiles;

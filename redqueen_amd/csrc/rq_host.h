@@ -53,7 +53,7 @@ struct SweepInst {
 #define RQ_FWS_NL 66
 #define RQ_FWS_LDS_BYTES(nK) ((size_t)8 * (((nK) + 2 + 3) * RQ_FWS_NL + 4))
 
-// The sink-tiled follower kernels (rq_followers_tiled.hip): sink columns per tile.  A tile's
+// The sink-tiled follower kernels (rq_followers.hip): sink columns per tile.  A tile's
 // per-sink state -- 12 + 8 (nK + 2) bytes, 8 more with row counts -- lives in one workgroup's
 // 160 KiB of LDS whatever nK and the counts, so TS <= 2409; 2048 is the measured choice
 // (-DRQ_FOLLOWERS_TILE_SINKS=... builds the other for the A/B).

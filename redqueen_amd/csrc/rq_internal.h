@@ -412,7 +412,7 @@ struct FollowersArgs {
 };
 hipError_t rq_launch_followers(const FollowersArgs& a, hipStream_t s);
 
-// ---- the same past the LDS sink limit: sink tiles + an r2 pass (rq_followers_tiled.hip) ----
+// ---- the same past the LDS sink limit: sink tiles + an r2 pass (rq_followers.hip) ----
 struct FollowersTiledArgs {
     FollowersArgs f;          // f.log: the graph's full CSR (the r2 pass)
     const int* tile_ptr;      // [n_tiles][n_str + 1] into tile_col (GraphTopo)

@@ -1,7 +1,8 @@
 // rq_log_walk.h -- what the kernels that replay a batch's compact event logs share
 // (rq_timeline.hip, rq_followers.hip, rq_rank_hist.hip): the view of the logs and the
 // graph, the chunked log reader, the rank rule, the time-bin clipper and the status.
-// Each kernel runs one wavefront per replica and keeps its own per-sink state in LDS.
+// Each kernel runs one wavefront per replica (the followers' tile kernel: per replica and
+// tile of sink columns) and keeps its own per-sink state in LDS.
 // rq_followers.hip and rq_rank_hist.hip read their logs through log_walk, and the rank
 // histogram clips through BinClip; rq_timeline.hip keeps the same text of both inline,
 // where it holds its measured time.

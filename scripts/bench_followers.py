@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Time rq_log_followers on the C3 network (graphs.c3, as bench.py builds it): R replicas
-with their event logs, nK = 1.  Beside it, on the same logs:
+with their event logs, nK = 1 (--nk N: Ks = 1..N).  Beside it, on the same logs:
 
-  (a) rq_log_followers, rows = NULL
+  (a) rq_log_followers, rows = NULL (--rows: with the own / wall row counts)
   (b) rq_log_timeline with one bin: the sibling kernel that makes the same walk
   (c) the route (a) replaces: log_columns() (rq_log_rows + rq_log_expand, 40 B per
       (event, sink) row), the pivot's column index and unique-time count of every
@@ -18,7 +18,8 @@ slowest and all repeats are reported.  Before anything is timed (a) is compared 
 run's own metrics (the mean over the seen sinks of the per-sink top-1 integrals is the
 sweep's top_1) and (c)'s unique-time counts with the run's pivot rows.
 
-    python scripts/bench_followers.py [--replicas 1024] [--reps 7] [--sample 32] [--out FILE]
+    python scripts/bench_followers.py [--replicas 1024] [--reps 7] [--sample 32] [--nk 1] [--rows]
+                                      [--out FILE]
 """
 import argparse
 import json
@@ -37,6 +38,8 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--sample", type=int, default=32)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--nk", type=int, default=1, help="route (a) with Ks = 1..nk")
+    ap.add_argument("--rows", action="store_true", help="route (a) with the row counts")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "followers_c3.json"))
     a = ap.parse_args()
     import torch
@@ -58,8 +61,10 @@ def main():
     index = torch.empty(n_t_max, dtype=torch.float64, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
 
+    Ks = tuple(range(1, a.nk + 1))
+
     def route_a():
-        return res.followers()
+        return res.followers(Ks=Ks, rows=a.rows)
 
     def route_b():
         return res.timeline(bins=1)
@@ -134,8 +139,9 @@ def main():
         if it >= a.warmup:
             for k, v in zip(ms, (ta, tb, tp, tt)):
                 ms[k].append(v)
-    lds = g.n_sinks * (12 + 8 * 3)
-    rec = {"network": "C3 (graphs.c3)", "replicas": R, "nK": 1, "events": events, "rows": rows,
+    lds = g.n_sinks * (12 + 8 * (a.nk + 2) + (8 if a.rows else 0))
+    rec = {"network": "C3 (graphs.c3)", "replicas": R, "nK": a.nk, "row_counts": a.rows, "events": events,
+           "rows": rows,
            "sinks": g.n_sinks, "reps": a.reps, "warmup": a.warmup,
            "c_sample_replicas": int(len(sample)),
            "top1_vs_metrics_max_rel": rel, "lds_bytes_per_block": lds,

@@ -4,6 +4,8 @@ raw ABI calls, every output buffer of which carries a 64-element sentinel guard.
 import numpy as np
 import pytest
 
+from tests import followers_ref as FR
+
 GUARD = 64
 D_SENT, I_SENT = -1.2345e300, -7777
 
@@ -125,6 +127,33 @@ def raw_followers_dev(torch, L, g, dt, ds, dc, Ks, rows=True, expect=0):
 
 def raw_followers(torch, L, g, ev_t, ev_src, counts, Ks, rows=True, expect=0):
     return raw_followers_dev(torch, L, g, *_dev(torch, ev_t, ev_src, counts), Ks, rows, expect)
+
+
+def assert_replica(out, i, ref, what, rows=True):
+    """Replica i of a raw followers call / followers_host dict against the checker
+    (tests/followers_ref.py): bit for bit."""
+    assert out["status"][i] == ref["status"], (what, out["status"][i], ref["status"])
+    assert FR.same_bits(out["vals"][i], ref["vals"]), what
+    assert FR.same_bits(out["r2_true"][i], ref["r2_true"]), (what, out["r2_true"][i], ref["r2_true"])
+    assert FR.same_bits(out["first_t"][i], ref["first_t"]), what
+    if rows:
+        assert np.array_equal(out["rows"][i], ref["rows"]), what
+
+
+def assert_same(a, b, what, rows=True):
+    """Two followers results of one batch: bit for bit."""
+    for k in ("vals", "first_t", "r2_true"):
+        assert FR.same_bits(a[k], b[k]), (what, k)
+    assert np.array_equal(a["status"], b["status"]), what
+    if rows:
+        assert np.array_equal(a["rows"], b["rows"]), what
+
+
+def followers_host(fl):
+    """An engine.Followers as the dict of numpy arrays that the raw calls return."""
+    return dict(vals=fl.vals.cpu().numpy(), first_t=fl.first_t.cpu().numpy(),
+                rows=None if fl.rows is None else fl.rows.cpu().numpy(),
+                r2_true=fl.r_2_true.cpu().numpy(), status=fl.status.cpu().numpy())
 
 
 def raw_rank_hist(torch, L, g, ev_t, ev_src, counts, edges, nr, expect=0, cap=None):

@@ -16,29 +16,12 @@ import pytest
 
 from tests import followers_ref as FR
 from tests import timeline_ref as TR
-from tests.loghelp import (ctx as _ctx, degrees_world as _degrees_world, graph as _graph, pack,
-                           raw_followers as _raw, raw_followers_dev as _raw_dev)
+from tests.loghelp import (assert_replica as _assert_replica, ctx as _ctx, degrees_world as _degrees_world,
+                           followers_host as _host, graph as _graph, pack, raw_followers as _raw,
+                           raw_followers_dev as _raw_dev)
 
 pytestmark = pytest.mark.gpu
 _pack = functools.partial(pack, full=True)   # a log may fill its row here
-
-
-
-
-def _assert_replica(out, i, ref, what, rows=True):
-    """Replica i of a raw call / Followers dict against the checker: bit for bit."""
-    assert out["status"][i] == ref["status"], (what, out["status"][i], ref["status"])
-    assert FR.same_bits(out["vals"][i], ref["vals"]), what
-    assert FR.same_bits(out["r2_true"][i], ref["r2_true"]), (what, out["r2_true"][i], ref["r2_true"])
-    assert FR.same_bits(out["first_t"][i], ref["first_t"]), what
-    if rows:
-        assert np.array_equal(out["rows"][i], ref["rows"]), what
-
-
-def _host(fl):
-    return dict(vals=fl.vals.cpu().numpy(), first_t=fl.first_t.cpu().numpy(),
-                rows=None if fl.rows is None else fl.rows.cpu().numpy(),
-                r2_true=fl.r_2_true.cpu().numpy(), status=fl.status.cpu().numpy())
 
 
 def _assert_close(got, exp, rows, what):

@@ -11,8 +11,9 @@ import numpy as np
 import pytest
 
 from tests import followers_ref as FR
-from tests.loghelp import (D_SENT, GUARD, I_SENT, _dev, ctx as _ctx, degrees_world as _degrees_world,
-                           graph as _graph, pack, raw_followers_dev as _raw_old_dev)
+from tests.loghelp import (D_SENT, GUARD, I_SENT, _dev, assert_replica as _assert_replica,
+                           assert_same as _assert_same, ctx as _ctx, degrees_world as _degrees_world,
+                           followers_host as _host, graph as _graph, pack, raw_followers_dev as _raw_old_dev)
 
 pytestmark = pytest.mark.gpu
 
@@ -78,34 +79,11 @@ def _raw(torch, L, g, ev_t, ev_src, counts, Ks, rows=True, **kw):
     return _raw_dev(torch, L, g, *_dev(torch, ev_t, ev_src, counts), Ks, rows, **kw)
 
 
-def _assert_replica(out, i, ref, what, rows=True):
-    assert out["status"][i] == ref["status"], (what, out["status"][i], ref["status"])
-    assert FR.same_bits(out["vals"][i], ref["vals"]), what
-    assert FR.same_bits(out["r2_true"][i], ref["r2_true"]), (what, out["r2_true"][i], ref["r2_true"])
-    assert FR.same_bits(out["first_t"][i], ref["first_t"]), what
-    if rows:
-        assert np.array_equal(out["rows"][i], ref["rows"]), what
-
-
-def _assert_same(a, b, what, rows=True):
-    for k in ("vals", "first_t", "r2_true"):
-        assert FR.same_bits(a[k], b[k]), (what, k)
-    assert np.array_equal(a["status"], b["status"]), what
-    if rows:
-        assert np.array_equal(a["rows"], b["rows"]), what
-
-
 def _prefix(ref4, nK):
     """The checker's result for the first nK of its 4 K values (a K's integral does not
     depend on the other Ks: the columns are [top_K..., rank, rank^2])."""
     v = ref4["vals"]
     return dict(ref4, vals=np.concatenate([v[:, :nK], v[:, 4:]], axis=1))
-
-
-def _host(fl):
-    return dict(vals=fl.vals.cpu().numpy(), first_t=fl.first_t.cpu().numpy(),
-                rows=None if fl.rows is None else fl.rows.cpu().numpy(),
-                r2_true=fl.r_2_true.cpu().numpy(), status=fl.status.cpu().numpy())
 
 
 # ------------------------------------------------- 1. the old entry's bits
