@@ -289,7 +289,10 @@ int rq_plan_info(rq_graph_t g, const rq_batch_desc* b, int64_t* info);
 /* the first n entries of the same list, which continues: [8] the sweep integrates each
  * replica's rows itself and the chunk launches no scan kernel (1; the merged fused sweep
  * without event log or max_events, RQ_SWEEP_SCAN=0 in the environment turns it off) or the
- * scan kernel runs after the sweep (0).  Entries past the last defined one are not written. */
+ * scan kernel runs after the sweep (0); [9] the merged fused sweep on K=1 sink bitsets
+ * counts a tile's top-1 sets with its events blocked four to a lane (1; graphs of at least
+ * 385 sinks, RQ_PHASEC_BLK=0 in the environment turns it off) or one event per lane (0).
+ * Entries past the last defined one are not written. */
 int rq_plan_info_n(rq_graph_t g, const rq_batch_desc* b, int64_t* info, int n);
 
 int rq_run_batch(rq_graph_t g, const rq_batch_desc* b, const rq_outputs* out,

@@ -650,12 +650,13 @@ int rq_plan_info(rq_graph_t g, const rq_batch_desc* b, int64_t* info)
 int rq_plan_info_n(rq_graph_t g, const rq_batch_desc* b, int64_t* out, int n)
 {
     if (!out || n < 0) return RQ_EINVAL;
-    int64_t info[9];
+    int64_t info[10];
     Plan p;
     const int rc = plan_call(g, b, rqh::read_knobs(), 0.0, &p);
     if (rc) return rc;
     rqh::plan_info(p, b->ctrl_kind, info);
-    std::copy(info, info + std::min(n, 9), out);
+    info[9] = p.blk ? 1 : 0;
+    std::copy(info, info + std::min(n, 10), out);
     return RQ_OK;
 }
 

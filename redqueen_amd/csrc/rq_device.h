@@ -123,6 +123,19 @@ __device__ __forceinline__ int64_t bcast_i64(int64_t v, int src_lane)
     return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
+// An LDS pointer through a 32-bit address the compiler knows nothing about: a loop that bumps
+// it keeps one v_add per trip, where an offset from the dynamic LDS base (an absolute symbol,
+// zero) costs the bump and an add of the base each trip.  Still an LDS pointer to the
+// compiler (ds_ instructions, not flat ones).
+template <class T>
+__device__ __forceinline__ T* lds_opaque(T* p)
+{
+    typedef __attribute__((address_space(3))) char* lds_ptr;
+    uint32_t a = (uint32_t)(size_t)(lds_ptr)(char*)p;
+    __asm__("" : "+v"(a));
+    return (T*)(char*)(lds_ptr)(size_t)a;
+}
+
 // order this wave's LDS stores before its later LDS loads of other lanes' data
 __device__ __forceinline__ void wave_lds_sync()
 {
@@ -305,6 +318,58 @@ struct SegFlags {
         v += dpp0<0x142, 0xA>(v) & c4;
         v += dpp0<0x143, 0xC>(v) & c5;
         return v;
+    }
+};
+
+// The same segmented OR scan with the tile's events blocked four to a lane: lane 16 b + g
+// holds events 4g .. 4g + 3 for the words of column block b, one DPP row per block.  The
+// first two levels of the scan are then ORs between a lane's own registers (chain), the
+// other four run over the 16 group totals of a row (carry) and never leave it.  Masks,
+// not selects, for SegFlags' reason.
+struct BlkFlags {
+    uint32_t c0, c1, c2, c3;   // 0 where event 4g + k is a segment head, else ~0
+    uint32_t d0, d1, d2, d3;   // SegFlags' first four masks over the groups' "holds a head" flags
+    uint32_t kc;               // ~0 in group 0 unless event 0 is a head: that lane takes the carried set
+    // rm: the tile's heads, bit e for event e (wave-uniform)
+    __device__ __forceinline__ void init(uint64_t rm, int lane)
+    {
+        const int g = lane & 15;
+        const uint32_t h = (uint32_t)(rm >> (4 * g)) & 0xFu;
+        c0 = (h & 1u) - 1u;
+        c1 = ((h >> 1) & 1u) - 1u;
+        c2 = ((h >> 2) & 1u) - 1u;
+        c3 = (h >> 3) - 1u;
+        uint32_t f = h ? 1u : 0u;
+        d0 = f - 1u;  f |= dpp0<0x111, 0xF>(f);
+        d1 = f - 1u;  f |= dpp0<0x112, 0xF>(f);
+        d2 = f - 1u;  f |= dpp0<0x114, 0xF>(f);
+        d3 = f - 1u;
+        kc = g == 0 ? c0 : 0u;
+        __asm__("" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3), "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3), "+v"(kc));
+    }
+    // m0..m3: one word of the four events' masks; u0..u3: the union since the segment start
+    // at each event, given the union p that reaches the group from the events before it
+    __device__ __forceinline__ void chain(uint32_t p, uint32_t m0, uint32_t m1, uint32_t m2, uint32_t m3, uint32_t& u0,
+                                          uint32_t& u1, uint32_t& u2, uint32_t& u3) const
+    {
+        u0 = m0 | (p & c0);
+        u1 = m1 | (u0 & c1);
+        u2 = m2 | (u1 & c2);
+        u3 = m3 | (u2 & c3);
+    }
+    // the union that reaches group g from the groups before it in the row (0 in group 0):
+    // the segmented inclusive scan of the group totals t, shifted down one group
+    __device__ __forceinline__ uint32_t carry(uint32_t t) const
+    {
+        uint32_t s = dppz<0x111>(t);
+        uint32_t v = t | (s & d0);
+        s = dppz<0x112>(v);
+        v |= s & d1;
+        s = dppz<0x114>(v);
+        v |= s & d2;
+        s = dppz<0x118>(v);
+        v |= s & d3;
+        return dppz<0x111>(v);
     }
 };
 

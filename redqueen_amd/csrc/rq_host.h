@@ -46,7 +46,20 @@ struct SweepInst {
                   //   lane every other tile, both of its draws used), else a call per draw
     bool scan;    // fused, mrg: the wave that swept a replica integrates its rows itself (rq_scan's
                   //   sums, written to SweepArgs.metrics; no rq_scan launch for the chunk)
+    bool blk;     // fused, mrg, bits: phase C with the tile's events blocked four to a lane
+                  //   (BlkFlags) once every sink has a row, else one event per lane throughout
 };
+// SweepInst.blk: lane 16 b + g scans events 4g .. 4g + 3 over the RQ_BLK_CB words of column
+// block b.  An even number of words per block (two columns per trip, 8-byte reads), so the
+// four blocks cover nw rounded up to 8 words; the pad words hold zero masks and zero F.  A
+// mask row is the four blocks plus 4 words: rows stay 16-byte aligned and start on 16 banks.
+// A tile pays the staging, the flags and the transposed sum of the counts whatever nw is
+// (about 85 VALU in the gfx950 code) and 65 per trip of two columns, where the word loop pays
+// 33 per trip of two words: 85 + 65 ceil(nw / 8) against 16.5 nw + 10 is the shorter one at 13
+// to 16 words and from 17 on.
+#define RQ_BLK_CB(nw) ((((nw) + 7) >> 3) << 1)
+#define RQ_BLK_MSTRIDE(nw) (4 * RQ_BLK_CB(nw) + 4)
+#define RQ_BLK_MIN_NW 13
 // SweepInst.scan: the per-wave LDS of the sweep's scan, aliased on the wave's sweep area
 // (dead after the tile loop, initialised again at the top of each replica); the layout of
 // rq::npsum_lds_doubles<nK + 2, RQ_FWS_NL>() -- 66 leaf slots, a block of 8192 rows has <= 65
@@ -120,6 +133,9 @@ struct Knobs {
     bool ctrl_draws = true;
     // RQ_SWEEP_SCAN=0: the scan kernel instead of the sweep's own scan; A/B, test_gpu_sweep_scan
     bool sweep_scan = true;
+    // RQ_PHASEC_BLK=0: the merged sink-bit sweep keeps one event per lane in phase C (the word
+    // loop); A/B, test_gpu_phase_c_blocked
+    bool phasec_blk = true;
     // RQ_FW_W: only this ring depth for the fused sweep (0: any); tuning (scripts/gpu_envab.sh)
     // and test_gpu_policy
     int fw_w = 0;
@@ -254,6 +270,9 @@ struct Plan {
     // fwm without event log or max_events: each wave integrates the rows of the replica it
     // swept (SweepInst.scan), the chunk launches no rq_scan; RQ_SWEEP_SCAN=0 keeps the kernel
     bool scan = false;
+    // fwm on sink bits with at least RQ_BLK_MIN_NW words: phase C event-blocked (SweepInst.blk),
+    // mask rows of RQ_BLK_MSTRIDE words; RQ_PHASEC_BLK=0 keeps the word loop and its stride
+    bool blk = false;
     // general sweep LDS layout
     int gwpb = 4, gwin = 16, gcol_lds = 1, gcol16 = 0;
     size_t g_col = 0, g_ptr = 0, g_odf = 0, g_cbf = 0, g_wave = 0, g_wave_stride = 0, g_rank_off = 0,

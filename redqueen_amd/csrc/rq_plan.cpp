@@ -24,6 +24,7 @@ Knobs read_knobs()
     if (const char* e = getenv("RQ_FWM")) k.fwm = atoi(e) != 0;
     if (const char* e = getenv("RQ_CTRL_DRAWS")) k.ctrl_draws = atoi(e) != 0;
     if (const char* e = getenv("RQ_SWEEP_SCAN")) k.sweep_scan = atoi(e) != 0;
+    if (const char* e = getenv("RQ_PHASEC_BLK")) k.phasec_blk = atoi(e) != 0;
     if (const char* e = getenv("RQ_FW_W")) k.fw_w = atoi(e);
     if (const char* e = getenv("RQ_PIPE")) k.pipe = std::max(1, std::min(3, atoi(e)));
     if (const char* e = getenv("RQ_PIPE_CHUNK")) k.pipe_chunk = {true, std::max<int64_t>(64, atoll(e))};
@@ -111,6 +112,7 @@ SweepInst sweep_inst(const Plan& p, int ctrl_kind, bool fused, int W, bool col16
     i.pw = ctrl_kind == RQ_SRC_OPTPW;   // exactly the runs rq_run_batch gives SweepArgs.pw_c
     i.pair = fused && i.mrg && p.pair;
     i.scan = fused && i.mrg && p.scan;
+    i.blk = fused && i.mrg && p.blk;
     return i;
 }
 int sweep_blocks_per_cu(const SweepInst& i, int wpb, size_t lds)
@@ -376,13 +378,17 @@ void plan_fused_lds(const GraphTopo* g, const rq_batch_desc* b, const Knobs& kn,
     p->pair = p->pair && kn.ctrl_draws;   // A/B and tests
     p->scan = p->fwm && !(b->flags & RQ_RUN_EVENT_LOG) && b->max_events < 0;
     p->scan = p->scan && kn.sweep_scan;   // A/B and tests
+    p->blk = p->fwm && p->bits && g->nw >= RQ_BLK_MIN_NW;
+    p->blk = p->blk && kn.phasec_blk;   // A/B and tests
+    // the mask rows' stride: the event-blocked phase C reads two words of a row at a time
+    const int mstride = p->blk ? RQ_BLK_MSTRIDE(g->nw) : p->mstride;
     if (p->fw) {
         int best = -1;
         const int c16 = p->bits ? 1 : (g->n_sinks <= 65535 ? 1 : 0);
         if (pw && !c16) p->fw = false;   // OptPWSignificance fused instances: uint16 columns
         // BITS: sink bitsets [n_str + 1][mstride] (row n_str all zero: the mask of a
         // lane without a wall event) replace the columns
-        const size_t colb = p->bits ? 4 * (size_t)(g->n_str + 1) * p->mstride
+        const size_t colb = p->bits ? 4 * (size_t)(g->n_str + 1) * mstride
                                     : (c16 ? 2 * g->csr_col.size() : 0);
         size_t sh = 0;
         const size_t o_col = sh;  sh = align_up(sh + colb, 16);
@@ -398,8 +404,10 @@ void plan_fused_lds(const GraphTopo* g, const rq_batch_desc* b, const Knobs& kn,
             if (W == 32 && !p->bits) continue;   // 32-deep rings: K = 1 bitset instance only
             const int H = W > 16 ? 8 : W / 2;    // register window
             const size_t r_off = align_up(8 * (size_t)g->n_str, 16);
-            // per wave: BITS -> (F, T) word pairs [nw]; else int16 sink ranks
-            const size_t w_off = align_up(r_off + (p->bits ? 8 * (size_t)((g->nw + 1) & ~1) : 2 * (size_t)p->n_sinks_pad), 16);
+            // per wave: BITS -> (F, T) word pairs [nw] (blk: of the four column blocks); else
+            // int16 sink ranks
+            const size_t ftw = p->blk ? 4 * (size_t)RQ_BLK_CB(g->nw) : (size_t)((g->nw + 1) & ~1);
+            const size_t w_off = align_up(r_off + (p->bits ? 8 * ftw : 2 * (size_t)p->n_sinks_pad), 16);
             // merged streams: no arrival rings
             const size_t s_off = align_up(w_off + (p->fwm ? 0 : 8 * (size_t)g->n_str * (W + 1)), 16);
             size_t stride = align_up(s_off + 64 * 12, 16);
@@ -426,7 +434,8 @@ void plan_fused_lds(const GraphTopo* g, const rq_batch_desc* b, const Knobs& kn,
         if (best < 0) p->fw = false;
     }
     if (!p->fw) p->fwm = false;
-    if (!p->fwm) p->pair = p->scan = false;
+    if (!p->fwm) p->pair = p->scan = p->blk = false;
+    if (p->blk) p->mstride = mstride;
     if (p->fw) p->mrg = p->fwm;   // the merge kernel feeds the fused sweep too
 }
 

@@ -80,11 +80,13 @@ __device__ __forceinline__ void fw_scan_rows(int64_t n, double S, double end, co
         for (int s = 0; s < NV; ++s) out[s] = res[s];
     }
 }
-template <int NK, class COL, int W, int H, bool BITS, bool PW, bool MRG, bool PAIR = false, bool SCAN = false>
+template <int NK, class COL, int W, int H, bool BITS, bool PW, bool MRG, bool PAIR = false, bool SCAN = false,
+          bool BLK = false>
 __device__ __forceinline__ void sweep_fw_body(SweepArgs a)
 {
     static_assert((W & (W - 1)) == 0 && H <= W, "ring");
     static_assert(!SCAN || MRG, "the sweep's own scan: merged instances only");
+    static_assert(!BLK || (MRG && BITS), "event-blocked phase C: the merged sink-bit instances only");
     extern __shared__ double lds_g[];
     char* base = reinterpret_cast<char*>(lds_g);
     const int lane = lane_id();
@@ -193,7 +195,8 @@ __device__ __forceinline__ void sweep_fw_body(SweepArgs a)
     AggB agb;
     if (BITS) {
         agb.init(msk, a.nw, ms, a.ctrl_idx, lane);
-        if (lane < ((a.nw + 1) & ~1)) ft[lane] = make_uint2(agb.F, 0u);   // agb.F = 0 past nw
+        // agb.F = 0 past nw; BLK: the pad words of the four column blocks too
+        if (lane < (BLK ? 4 * RQ_BLK_CB(a.nw) : (a.nw + 1) & ~1)) ft[lane] = make_uint2(agb.F, 0u);
     }
     RowStage<NK> rs;
     const int64_t rbase = rl * a.cap_rows;
@@ -429,7 +432,69 @@ __device__ __forceinline__ void sweep_fw_body(SweepArgs a)
             const bool wlast = lane == last;
             int cw = 0, vw = 0, vo = 0;
             uint32_t nV = agb.V;
-            if (vfull) {
+            if (BLK && vfull) {
+                // event-blocked (BlkFlags): lane 16 b + g takes events 4g .. 4g + 3 for the
+                // CB words of column block b.  The events' mask rows (word offsets into msk,
+                // the zero row for a lane without a wall event) go through the wave's stage
+                // area, which the merged instances do not use otherwise.
+                const int CB = RQ_BLK_CB(a.nw);
+                // the lane id opaque at each tile, so that what derives from it here is not
+                // hoisted out of the tile loop and spilled
+                int ln = lane;
+                __asm__ volatile("" : "+v"(ln));
+                int* st_r = reinterpret_cast<int*>(wb + a.lds_stage_off);
+                st_r[ln] = (wl ? tj : a.n_str) * ms;
+                wave_lds_sync();
+                const int g4 = ln & 15, cb0 = (ln >> 4) * CB;
+                const int4 ro = *reinterpret_cast<const int4*>(st_r + 4 * g4);
+                BlkFlags bf;
+                bf.init(rm, ln);
+                auto m0 = lds_opaque(reinterpret_cast<const uint2*>(msk + ro.x + cb0));
+                auto m1 = lds_opaque(reinterpret_cast<const uint2*>(msk + ro.y + cb0));
+                auto m2 = lds_opaque(reinterpret_cast<const uint2*>(msk + ro.z + cb0));
+                auto m3 = lds_opaque(reinterpret_cast<const uint2*>(msk + ro.w + cb0));
+                auto fb = lds_opaque(reinterpret_cast<uint4*>(ft + cb0));   // the block's F / T words
+                // events past the tile's last have zero masks and start no segment, so the
+                // union after the group's fourth event is the union after the last
+                const bool wgrp = g4 == (last >> 2);
+                uint32_t q0 = 0, q1 = 0, q2 = 0, q3 = 0;
+                // one column: F / carried T word f, the four events' mask words; returns the
+                // new T word.  Where event 0 is no head, group 0 ORs F & ~T into its mask:
+                // the events before the first head then see F & ~u = T & ~(wall union), T <= F
+                auto column = [&](uint2 f, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3)
+                                  __attribute__((always_inline)) -> uint32_t {
+                    w0 |= (f.x & ~f.y) & bf.kc;
+                    uint32_t l0, l1, l2, l3, u0, u1, u2, u3;
+                    bf.chain(0u, w0, w1, w2, w3, l0, l1, l2, l3);
+                    bf.chain(bf.carry(l3), w0, w1, w2, w3, u0, u1, u2, u3);
+                    q0 += __popc(f.x & ~u0);
+                    q1 += __popc(f.x & ~u1);
+                    q2 += __popc(f.x & ~u2);
+                    const uint32_t t3 = f.x & ~u3;
+                    q3 += __popc(t3);
+                    return t3;
+                };
+                // two columns per trip (CB is even), their chains interleaved
+                for (int c = 0; c < CB; c += 2, ++fb, ++m0, ++m1, ++m2, ++m3) {
+                    const uint4 f = *fb;
+                    const uint2 w0 = *m0, w1 = *m1, w2 = *m2, w3 = *m3;
+                    const uint32_t ta = column(make_uint2(f.x, f.y), w0.x, w1.x, w2.x, w3.x);
+                    const uint32_t tb = column(make_uint2(f.z, f.w), w0.y, w1.y, w2.y, w3.y);
+                    if (wgrp) {
+                        fb->y = ta;
+                        fb->w = tb;
+                    }
+                }
+                // q_k of lane 16 b + g: block b's part of event 4g + k's count.  Half swap and add:
+                // rows 0-1 hold k = 0 (from q0, q1) and k = 2 (from q2, q3), rows 2-3 k = 1 and
+                // k = 3, each over blocks b and b + 2; row swap and add: rows 0, 1, 2, 3 hold
+                // k = 0, 2, 1, 3 over the four blocks; lane e then fetches event e's count
+                const auto s01 = __builtin_amdgcn_permlane32_swap(q0, q1, false, false);
+                const auto s23 = __builtin_amdgcn_permlane32_swap(q2, q3, false, false);
+                const auto s4 = __builtin_amdgcn_permlane16_swap(s01[0] + s01[1], s23[0] + s23[1], false, false);
+                const int src = (((ln & 1) << 1 | ((ln >> 1) & 1)) << 4) | (ln >> 2);
+                cw = __builtin_amdgcn_ds_bpermute(src << 2, (int)(s4[0] + s4[1]));
+            } else if (vfull) {
                 // two words per trip (ft holds an even number of words, the pad word's F
                 // and T are zero), their DPP chains interleaved
                 for (int ww = 0; ww < a.nw; ww += 2) {
@@ -587,10 +652,10 @@ __global__ __launch_bounds__(1024) void rq_sweep_fw(SweepArgs a)
 #ifndef RQ_FWM_WPE
 #define RQ_FWM_WPE 4
 #endif
-template <int NK, class COL, bool BITS, bool PAIR = false, bool SCAN = false>
+template <int NK, class COL, bool BITS, bool PAIR = false, bool SCAN = false, bool BLK = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RQ_FWM_WPE))) void rq_sweep_fwm(SweepArgs a)
 {
-    sweep_fw_body<NK, COL, 16, 8, BITS, false, true, PAIR, SCAN>(a);
+    sweep_fw_body<NK, COL, 16, 8, BITS, false, true, PAIR, SCAN, BLK>(a);
 }
 
 // ============================================================================
@@ -619,11 +684,14 @@ static SweepKernel fwm_nk(int nK)
     default: return rq_sweep_fwm<4, COL, false, PAIR, SCAN>;
     }
 }
-// the merged instances: (call pairs) x (the sweep's own scan)
+// the merged instances: (call pairs) x (the sweep's own scan); the sink-bit ones x (phase C
+// event-blocked)
 template <bool PAIR, bool SCAN>
 static SweepKernel fwm_kernel(const SweepInst& i)
 {
-    if (i.bits) return rq_sweep_fwm<1, uint16_t, true, PAIR, SCAN>;
+    if (i.blk && !i.bits) return nullptr;
+    if (i.bits)
+        return i.blk ? rq_sweep_fwm<1, uint16_t, true, PAIR, SCAN, true> : rq_sweep_fwm<1, uint16_t, true, PAIR, SCAN>;
     return i.col16 ? fwm_nk<uint16_t, PAIR, SCAN>(i.nK) : fwm_nk<int, PAIR, SCAN>(i.nK);
 }
 // null: no such instance
@@ -635,7 +703,8 @@ static SweepKernel fw_kernel(const SweepInst& i)
             return i.scan ? fwm_kernel<true, true>(i) : fwm_kernel<true, false>(i);
         return i.scan ? fwm_kernel<false, true>(i) : fwm_kernel<false, false>(i);
     }
-    if (i.pair || i.scan) return nullptr;   // call pairs, the sweep's own scan: the merged instances only
+    // call pairs, the sweep's own scan, event-blocked phase C: the merged instances only
+    if (i.pair || i.scan || i.blk) return nullptr;
     // OptPWSignificance (PW) instances exist for uint16 columns and W = 16 only (make_plan
     // keeps other PW runs off this path)
     if (i.pw) {
@@ -674,6 +743,8 @@ hipError_t rq_launch_sweep_fw(const SweepArgs& a, const SweepInst& i, hipStream_
     // the sweep's own scan: its LDS inside the wave's area, no event log or max_events cut
     if (i.scan && (!a.metrics || a.ev_t || a.max_events >= 0 || a.lds_wave_stride < RQ_FWS_LDS_BYTES(i.nK)))
         return hipErrorInvalidValue;
+    // event-blocked phase C: the planner's row stride (8-byte reads of a block's words)
+    if (i.blk && a.mstride != RQ_BLK_MSTRIDE(a.nw)) return hipErrorInvalidValue;
     const SweepKernel k = fw_kernel(i);
     return k ? launch_fw_t(k, a, s) : hipErrorInvalidValue;
 }

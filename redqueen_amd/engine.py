@@ -333,10 +333,11 @@ class Graph:
         lib = L.lib()
         if plan_only:
             b.ws_budget = self._ws_budget(dev)
-            info = (C.c_int64 * 9)()
-            L.check("rq_plan_info_n", lib.rq_plan_info_n(self._h, C.byref(b), info, 9))
+            info = (C.c_int64 * 10)()
+            L.check("rq_plan_info_n", lib.rq_plan_info_n(self._h, C.byref(b), info, 10))
             keys = ("variant", "sources_per_lane", "ring_depth", "waves_per_block",
-                    "blocks_per_cu", "columns_in_lds", "lds_bytes_per_block", "chunk", "sweep_scan")
+                    "blocks_per_cu", "columns_in_lds", "lds_bytes_per_block", "chunk", "sweep_scan",
+                    "sweep_blk")
             return dict(zip(keys, (int(v) for v in info)))
         return self._run_loop(lib, b, keep, dev, R, Ks, n_grid, n_rep, ck, event_log,
                               gids, check, stream)
