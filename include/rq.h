@@ -44,6 +44,8 @@
  *                       the seen sink-time per rank value and time bin
  *                       utils.py:38-56, :84-98 (opt_runs.py:31-33's Ks curve)
  *                       for every replica of an RQ_RUN_EVENT_LOG batch at once
+ *   rq_log_game         Opt broadcasters among SimOpts.other_sources  opt_model.py:761,
+ *                       each Opt.get_next_interval :502-544 in run_dynamic's loop :271-309
  *
  * Conventions
  *   - every function returns 0 (RQ_OK) or a negative rq_status; no C++
@@ -566,6 +568,68 @@ int rq_log_rank_hist(rq_graph_t g, const double* ev_t, const int32_t* ev_src,
                      int32_t* max_rank,   /* device [n_rep] */
                      int32_t* status,     /* device [n_rep] */
                      void* hip_stream);
+
+/* Competing RedQueen broadcasters (Opt among SimOpts.other_sources, opt_model.py:493-544,
+ * :761): several Opts -- the PLAYERS -- post against each other and against an exogenous
+ * world in one run_dynamic loop (opt_model.py:271-309).  The sources no Opt influences
+ * (Poisson, Poisson2, Hawkes, PiecewiseConst, RealData, a static controlled source) are
+ * played first by rq_run_batch with RQ_RUN_EVENT_LOG; rq_log_game plays the players against
+ * that log and writes the completed log in the same layout, which every rq_log_* entry reads.
+ *   g is the REPLAY graph: every player is an RQ_SRC_REALDATA source flagged
+ * RQ_SRCF_DYNAMIC and declared with no times, or the controlled slot (else RQ_EINVAL).
+ * players: host [n_players], any order, distinct src_ids; player c has q > 0 and s[n_s] >= 0
+ * over its followers -- the distinct sinks of its edges in ascending sink id, n_s of them.
+ *   Rates.  C[c][j] = sum over stream j's edges (j, x), x a follower of c, of
+ * sqrt(s_c[x] / q_c), the terms added one by one from 0.0 in ascending sink id (a duplicated
+ * edge adds its term again); C[c][c] = 0; inv[c][j] = 1.0 / C[c][j], 0 where C is 0.
+ *   Play.  Every player's pending time T_c starts at the graph's start_time.  The pending
+ * post (T, c) of the player with the least (T, src_id) plays before the next exogenous entry
+ * (t, j) when T < t, or T == t and j is a static stream or src_id(c) < src_id(j)
+ * (opt_model.py:279-290); a post with T > end_time is never played; when the exogenous log is
+ * exhausted the players go on among themselves; play stops after max_events events (< 0:
+ * unbounded).  When event number e (0-based in the output) of stream j plays at time t:
+ * T_j = +inf if j is a player, and every other player c with inv[c][j] > 0 takes
+ * x = rq_std_exponential(rq_uniform53(w0, w1)), w = Philox4x32-10 of counter
+ * (lo32 e, hi32 e, 0, 0) under key (seeds[i][c], 0x52510006 | 0x100 if c is the controlled
+ * source), and sets T_c = min(T_c, t + x * inv[c][j]), product and sum each rounded.
+ *   seeds: device uint32 [n_rep][n_players], column c = players[c].  ev_t / ev_src / counts /
+ * ev_cap: the exogenous logs, rq_run_batch's layout (replica i plays its first
+ * min(counts[i][2], ev_cap) entries).  Outputs (device): out_t / out_src [n_rep][out_cap];
+ * out_counts [n_rep][4] with rq_outputs.counts' meaning (field 3 is 0); player_posts
+ * [n_rep][n_players] int64; status [n_rep]: RQ_ST_ROWS_OVERFLOW when an event was due with
+ * out_cap events written (the out_cap events written are the run's first: rerun with more),
+ * RQ_ST_EMPTY when no played event had an edge.  One wavefront plays a replica (lane c =
+ * the player with the c-th smallest src_id): no replica's bits depend on its neighbours,
+ * the launch or the batch.
+ *   workspace: device, rq_log_game_workspace bytes (the transposed inverse table
+ * [n_streams][n_players] and 4 bytes per stream); the call stages them through the graph's
+ * pinned ring exactly as rq_run_batch stages its tables (see Conventions), and otherwise only
+ * enqueues on hip_stream.  The table is read from LDS when rq_log_game_table_in_lds, else
+ * from global memory (any graph size).
+ *   RQ_EINVAL: a null pointer, n_rep < 1 (or > INT32_MAX), ev_cap < 0, out_cap < 1, a short
+ * workspace, or a player that is no stream of the graph / not a replay stream / named twice /
+ * with a duplicated follower edge / without followers / with n_s wrong / q <= 0 / an s < 0.
+ * RQ_EUNSUPPORTED: more than RQ_GAME_MAX_PLAYERS players.  A refused call launches nothing.
+ *   Added without an ABI version change (RQ_ABI_VERSION stays 6); a caller detects the
+ * functions by their symbols. */
+#define RQ_GAME_MAX_PLAYERS 64
+typedef struct rq_game_player {
+    int64_t src_id;
+    double q;
+    const double* s;   /* host [n_s], ascending follower sink id */
+    int32_t n_s;
+} rq_game_player;
+int rq_log_game_workspace(rq_graph_t g, int32_t n_players, size_t* bytes);
+int32_t rq_log_game_table_in_lds(rq_graph_t g, int32_t n_players);   /* 1 LDS, 0 global */
+int rq_log_game(rq_graph_t g, const rq_game_player* players, int32_t n_players,
+                const uint32_t* seeds,                        /* device [n_rep][n_players] */
+                const double* ev_t, const int32_t* ev_src, const int64_t* counts,
+                int64_t n_rep, int64_t ev_cap, int64_t max_events,
+                double* out_t, int32_t* out_src, int64_t out_cap,
+                int64_t* out_counts,                          /* device [n_rep][4] */
+                int64_t* player_posts,                        /* device [n_rep][n_players] */
+                int32_t* status,                              /* device [n_rep] */
+                void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /* Per-kernel timing for benchmarks: rq_timing(1) starts recording HIP events
  * around every kernel this library launches (on the caller's stream);

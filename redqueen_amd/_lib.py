@@ -110,6 +110,14 @@ class Outputs(C.Structure):
                 ("ev_src", _P), ("ev_cap", C.c_int64)]
 
 
+class GamePlayer(C.Structure):
+    """rq_game_player: one Opt of rq_log_game (s over its sorted followers, host)."""
+    _fields_ = [("src_id", C.c_int64), ("q", C.c_double), ("s", _pd), ("n_s", C.c_int32)]
+
+
+GAME_MAX_PLAYERS = 64   # RQ_GAME_MAX_PLAYERS
+
+
 class RQError(RuntimeError):
     def __init__(self, fn, code):
         self.code = code
@@ -169,6 +177,14 @@ def lib():
     L.rq_log_rank_hist.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int32,
                                    _P, _P, _P, _P, _P]
     L.rq_log_followers_max_sinks.restype = C.c_int32
+    # added without an ABI version change: a library without the symbols raises here
+    L.rq_log_game_workspace.argtypes = [_P, C.c_int32, C.POINTER(C.c_size_t)]
+    L.rq_log_game_workspace.restype = C.c_int
+    L.rq_log_game_table_in_lds.argtypes = [_P, C.c_int32]
+    L.rq_log_game_table_in_lds.restype = C.c_int32
+    L.rq_log_game.argtypes = [_P, C.POINTER(GamePlayer), C.c_int32, _P, _P, _P, _P, C.c_int64,
+                              C.c_int64, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_size_t, _P]
+    L.rq_log_game.restype = C.c_int
     L.rq_timing.argtypes = [C.c_int]
     L.rq_timing_read.argtypes = [_pd, _pi64]
     for fn in ("rq_timing", "rq_timing_read", "rq_graph_build", "rq_graph_free", "rq_graph_info", "rq_graph_source_ids",
@@ -225,5 +241,6 @@ EXPORTED = ["rq_abi_version", "rq_strerror", "rq_graph_build", "rq_graph_free", 
             "rq_metrics_replay", "rq_metrics_replay_batch", "rq_oracle_workspace_size", "rq_oracle_dp", "rq_rank_table",
             "rq_u_int", "rq_log_rows", "rq_log_expand", "rq_log_timeline", "rq_log_followers",
             "rq_log_followers_tiled_workspace", "rq_log_followers_tiled",
-            "rq_log_rank_hist", "rq_timing", "rq_timing_read"]
-# rq_log_followers_max_sinks and rq_log_followers_tile_sinks return int32_t, no status
+            "rq_log_rank_hist", "rq_log_game_workspace", "rq_log_game", "rq_timing", "rq_timing_read"]
+# rq_log_followers_max_sinks, rq_log_followers_tile_sinks and rq_log_game_table_in_lds return
+# int32_t, no status

@@ -27,6 +27,8 @@ def _val_key(v):
         a = np.ascontiguousarray(np.asarray(v))
         if a.dtype != object:
             return (str(a.dtype), a.shape, hashlib.sha1(a.tobytes()).hexdigest())
+    if isinstance(v, dict):   # an Opt's s by sink id: whatever the insertion order
+        return tuple(sorted((repr(k), _val_key(x)) for k, x in v.items()))
     return repr(v)
 
 

@@ -243,16 +243,17 @@ int plan_call(const rq_graph* g, const rq_batch_desc* b, const Knobs& kn, double
 // Parameter tables [inv_c | st_off | cap | rd_k | rep_idx | pw_c | pw_max] to the start of
 // the workspace: staged in one of the graph's pinned host buffers so the copy is truly
 // asynchronous (a pageable copy would stall the host)
-int stage_tables(rq_graph* g, const Plan& p, const rq_batch_desc* b, const CtrlTables& t, char* ws,
-                 hipStream_t s)
+// The next slot of the graph's pinned ring, at least `bytes` large and free again (the copy
+// issued from it four calls ago is done).  The caller holds stage_mu, fills slot->buf, copies
+// from it on its stream and records slot->done there.
+int stage_slot(rq_graph* g, size_t bytes, Stage** slot)
 {
-    std::lock_guard<std::mutex> lk(g->stage_mu);
     Stage& st = g->stage[g->stage_next];
     g->stage_next = (g->stage_next + 1) % kStages;
-    if (st.bytes < p.tables_bytes) {
+    if (st.bytes < bytes) {
         // grow the whole ring at once (pinned allocation is slow: never leave a stage
         // to be allocated by a later, possibly timed, call); round up to 64 KiB
-        const size_t want = align_up(p.tables_bytes, (size_t)65536);
+        const size_t want = align_up(bytes, (size_t)65536);
         for (Stage& x : g->stage) {
             if (x.done && hipEventSynchronize(x.done) != hipSuccess) return RQ_EHIP;
             if (x.bytes >= want) continue;
@@ -266,6 +267,18 @@ int stage_tables(rq_graph* g, const Plan& p, const rq_batch_desc* b, const CtrlT
         }
     }
     if (st.done && hipEventSynchronize(st.done) != hipSuccess) return RQ_EHIP;
+    *slot = &st;
+    return RQ_OK;
+}
+
+int stage_tables(rq_graph* g, const Plan& p, const rq_batch_desc* b, const CtrlTables& t, char* ws,
+                 hipStream_t s)
+{
+    std::lock_guard<std::mutex> lk(g->stage_mu);
+    Stage* slot = nullptr;
+    const int rc = stage_slot(g, p.tables_bytes, &slot);
+    if (rc != RQ_OK) return rc;
+    Stage& st = *slot;
     char* tab = (char*)st.buf;
     std::memcpy(tab + p.off_invc, t.invc.data(), t.invc.size() * sizeof(double));
     std::memcpy(tab + p.off_stoff, p.st_off.data(), p.st_off.size() * sizeof(int64_t));
@@ -1209,6 +1222,90 @@ int rq_log_rank_hist(rq_graph_t g, const double* ev_t, const int32_t* ev_src, co
     hipStream_t st = (hipStream_t)hip_stream;
     TimedLaunch tl(K_REPLAY, st);
     return rq_launch_rank_hist(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
+}
+
+int rq_log_game_workspace(rq_graph_t g, int32_t n_players, size_t* bytes)
+{
+    if (!g || !bytes || n_players < 1) return RQ_EINVAL;
+    if (n_players > RQ_GAME_MAX_PLAYERS) return RQ_EUNSUPPORTED;
+    *bytes = rqh::game_ws_bytes(g->n_str, n_players);
+    return RQ_OK;
+}
+
+int32_t rq_log_game_table_in_lds(rq_graph_t g, int32_t n_players)
+{
+    if (!g || n_players < 1 || n_players > RQ_GAME_MAX_PLAYERS) return 0;
+    return rqh::game_table_in_lds(g->n_str, n_players) ? 1 : 0;
+}
+
+// the players' tables [inv | meta | lane_stream | lane_col] to the workspace, through the
+// graph's pinned ring (stage_tables' protocol: the copy is truly asynchronous)
+static int stage_game(rq_graph* g, const rqh::GameTables& t, char* ws, hipStream_t s)
+{
+    const size_t bytes = rqh::game_ws_bytes(g->n_str, t.P);
+    std::lock_guard<std::mutex> lk(g->stage_mu);
+    Stage* slot = nullptr;
+    const int rc = stage_slot(g, bytes, &slot);
+    if (rc != RQ_OK) return rc;
+    Stage& st = *slot;
+    char* tab = (char*)st.buf;
+    std::memset(tab, 0, bytes);
+    const size_t off_l = rqh::game_ws_off_lanes(g->n_str, t.P);
+    std::memcpy(tab, t.inv.data(), t.inv.size() * sizeof(double));
+    std::memcpy(tab + rqh::game_ws_off_meta(g->n_str, t.P), t.meta.data(), t.meta.size() * sizeof(int));
+    std::memcpy(tab + off_l, t.lane_stream.data(), t.lane_stream.size() * sizeof(int));
+    std::memcpy(tab + off_l + 256, t.lane_col.data(), t.lane_col.size() * sizeof(int));
+    if (hipMemcpyAsync(ws, tab, bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipEventRecord(st.done, s) != hipSuccess)
+        return RQ_EHIP;
+    return RQ_OK;
+}
+
+int rq_log_game(rq_graph_t g, const rq_game_player* players, int32_t n_players, const uint32_t* seeds,
+                const double* ev_t, const int32_t* ev_src, const int64_t* counts, int64_t n_rep,
+                int64_t ev_cap, int64_t max_events, double* out_t, int32_t* out_src, int64_t out_cap,
+                int64_t* out_counts, int64_t* player_posts, int32_t* status, void* workspace,
+                size_t workspace_bytes, void* hip_stream)
+{
+    if (!g || !players || !seeds || !ev_t || !ev_src || !counts || !out_t || !out_src || !out_counts ||
+        !player_posts || !status || !workspace)
+        return RQ_EINVAL;
+    if (n_rep < 1 || n_rep > INT32_MAX || ev_cap < 0 || out_cap < 1) return RQ_EINVAL;
+    rqh::GameTables t;
+    const int rc = rqh::game_tables(*g, players, n_players, &t);
+    if (rc != RQ_OK) return rc;
+    if (workspace_bytes < rqh::game_ws_bytes(g->n_str, t.P)) return RQ_EINVAL;
+    hipStream_t st = (hipStream_t)hip_stream;
+    char* ws = static_cast<char*>(workspace);
+    const int rs = stage_game(g, t, ws, st);
+    if (rs != RQ_OK) return rs;
+    GameArgs a{};
+    a.ev_t = ev_t;
+    a.ev_src = ev_src;
+    a.counts = counts;
+    a.n_rep = n_rep;
+    a.ev_cap = ev_cap;
+    a.max_events = max_events;
+    a.n_str = g->n_str;
+    a.P = t.P;
+    a.ctrl_lane = t.ctrl_lane;
+    a.ctrl_idx = g->ctrl_idx;
+    a.inv = reinterpret_cast<const double*>(ws);
+    a.meta = reinterpret_cast<const int*>(ws + rqh::game_ws_off_meta(g->n_str, t.P));
+    a.lane_stream = reinterpret_cast<const int*>(ws + rqh::game_ws_off_lanes(g->n_str, t.P));
+    a.lane_col = a.lane_stream + 64;
+    a.in_lds = rqh::game_table_in_lds(g->n_str, t.P) ? 1 : 0;
+    a.seeds = seeds;
+    a.start = g->start;
+    a.end = g->end;
+    a.out_t = out_t;
+    a.out_src = out_src;
+    a.out_cap = out_cap;
+    a.out_counts = out_counts;
+    a.player_posts = player_posts;
+    a.status = status;
+    TimedLaunch tl(K_SWEEP, st);
+    return rq_launch_game(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
 }
 
 }  // extern "C"

@@ -309,4 +309,37 @@ struct CtrlTables {
 };
 CtrlTables ctrl_tables(const GraphTopo& g, const rq_batch_desc* b);
 
+// ---- the players' rate tables of rq_log_game (include/rq.h) ----
+// Lane c of the game kernel is the player with the c-th smallest src_id, so the lowest lane
+// among equal pending times is the reference's tie winner.
+struct GameTables {
+    int P = 0;                      // players
+    int ctrl_lane = -1;             // the lane of the controlled source, if it plays
+    std::vector<int> lane_stream;   // [P] the lane's stream index
+    std::vector<int> lane_col;      // [P] the lane's position in the caller's players[] (seed column)
+    std::vector<double> C;          // [P][n_str] by lane
+    std::vector<double> inv;        // [n_str][P] transposed: 1 / C, 0 where C is 0
+    // per stream: bits 0-7 = the lanes [0, k) whose post plays before an entry of this stream
+    // at an equal time (P for a static stream, else the players of smaller src_id);
+    // bit 8 = the stream has an edge
+    std::vector<int> meta;
+};
+#define RQ_GAME_META_EDGE 256
+// LDS bytes the transposed table may take (4 waves a block share it; 64 KiB leaves two blocks a CU)
+#define RQ_GAME_LDS_TABLE_BYTES (64 * 1024)
+inline size_t game_table_bytes(int n_str, int P) { return (size_t)n_str * (size_t)P * sizeof(double); }
+inline bool game_table_in_lds(int n_str, int P) { return game_table_bytes(n_str, P) <= RQ_GAME_LDS_TABLE_BYTES; }
+// workspace of rq_log_game: [inv | meta | lane_stream | lane_col], each rounded up to 256 bytes
+inline size_t game_ws_off_meta(int n_str, int P) { return align_up(game_table_bytes(n_str, P), 256); }
+inline size_t game_ws_off_lanes(int n_str, int P)
+{
+    return game_ws_off_meta(n_str, P) + align_up((size_t)n_str * sizeof(int), 256);
+}
+inline size_t game_ws_bytes(int n_str, int P)
+{
+    return game_ws_off_lanes(n_str, P) + 2 * align_up((size_t)RQ_GAME_MAX_PLAYERS * sizeof(int), 256);
+}
+// RQ_OK, or the rq_status rq_log_game returns for these players on this graph
+int game_tables(const GraphTopo& g, const rq_game_player* players, int n_players, GameTables* out);
+
 }  // namespace rqh

@@ -434,3 +434,26 @@ struct RankHistArgs {
     int32_t* status;          // [n_rep]
 };
 hipError_t rq_launch_rank_hist(const RankHistArgs& a, hipStream_t s);
+
+// ---- competing RedQueen broadcasters against an exogenous log (rq_game.hip) ----
+struct GameArgs {
+    const double* ev_t;       // [n_rep][ev_cap] the exogenous logs
+    const int32_t* ev_src;    // [n_rep][ev_cap]
+    const int64_t* counts;    // [n_rep][4], [2] = entries
+    int64_t n_rep, ev_cap, max_events;
+    int n_str, P, ctrl_lane, ctrl_idx;
+    const double* inv;        // [n_str][P] (rqh::GameTables.inv)
+    const int* meta;          // [n_str]    (rqh::GameTables.meta)
+    int in_lds;               // inv copied to the block's LDS
+    const uint32_t* seeds;    // [n_rep][P], column = lane_col
+    double start, end;
+    double* out_t;            // [n_rep][out_cap]
+    int32_t* out_src;         // [n_rep][out_cap]
+    int64_t out_cap;
+    int64_t* out_counts;      // [n_rep][4]
+    int64_t* player_posts;    // [n_rep][P], column = lane_col
+    int32_t* status;          // [n_rep]
+    const int* lane_stream;   // [P] (device copies of rqh::GameTables' lane tables)
+    const int* lane_col;      // [P]
+};
+hipError_t rq_launch_game(const GameArgs& a, hipStream_t s);

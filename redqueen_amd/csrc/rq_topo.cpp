@@ -291,4 +291,78 @@ CtrlTables ctrl_tables(const GraphTopo& g, const rq_batch_desc* b)
     return t;
 }
 
+int game_tables(const GraphTopo& g, const rq_game_player* players, int n_players, GameTables* out)
+{
+    if (!players || !out || n_players < 1) return RQ_EINVAL;
+    if (n_players > RQ_GAME_MAX_PLAYERS) return RQ_EUNSUPPORTED;
+    const int P = n_players;
+    struct L { int64_t id; int col, stream; };
+    std::vector<L> lanes;
+    for (int c = 0; c < P; ++c) {
+        const rq_game_player& p = players[c];
+        int j = -1;
+        for (int k = 0; k < g.n_str; ++k)
+            if (g.src_id[k] == p.src_id) j = k;
+        if (j < 0) return RQ_EINVAL;   // not a stream of the graph
+        // a replay stream: the controlled slot, or a dynamic RealData source without times
+        const bool replay = j == g.ctrl_idx ||
+                            (g.kind[j] == RQ_SRC_REALDATA && !g.is_static[j] && g.arr_n[j] == 0);
+        if (!replay) return RQ_EINVAL;
+        if (!(p.q > 0.0) || p.n_s < 1 || !p.s) return RQ_EINVAL;
+        lanes.push_back({p.src_id, c, j});
+    }
+    std::sort(lanes.begin(), lanes.end(), [](const L& a, const L& b) { return a.id < b.id; });
+    for (int c = 1; c < P; ++c)
+        if (lanes[c].id == lanes[c - 1].id) return RQ_EINVAL;   // a player named twice
+
+    GameTables t;
+    t.P = P;
+    t.C.assign((size_t)P * g.n_str, 0.0);
+    t.inv.assign((size_t)g.n_str * P, 0.0);
+    std::vector<double> w(g.n_sinks);
+    std::vector<int> row;
+    for (int c = 0; c < P; ++c) {
+        const rq_game_player& p = players[lanes[c].col];
+        const int jc = lanes[c].stream;
+        t.lane_stream.push_back(jc);
+        t.lane_col.push_back(lanes[c].col);
+        if (jc == g.ctrl_idx) t.ctrl_lane = c;
+        // the player's followers: the distinct sinks of its edges, ascending (columns are in
+        // ascending sink id); a duplicated own edge is the reference's shape error
+        std::vector<int> fc(g.csr_col_el.begin() + g.csr_ptr[jc], g.csr_col_el.begin() + g.csr_ptr[jc + 1]);
+        std::sort(fc.begin(), fc.end());
+        if (fc.empty()) return RQ_EINVAL;
+        if (std::adjacent_find(fc.begin(), fc.end()) != fc.end()) return RQ_EINVAL;
+        if ((int)fc.size() != p.n_s) return RQ_EINVAL;
+        std::fill(w.begin(), w.end(), -1.0);   // -1: no follower of c
+        for (int f = 0; f < p.n_s; ++f) {
+            if (!(p.s[f] >= 0.0)) return RQ_EINVAL;
+            w[fc[f]] = std::sqrt(p.s[f] / p.q);
+        }
+        for (int j = 0; j < g.n_str; ++j) {
+            if (j == jc) continue;
+            row.assign(g.csr_col_el.begin() + g.csr_ptr[j], g.csr_col_el.begin() + g.csr_ptr[j + 1]);
+            std::sort(row.begin(), row.end());   // ascending sink id, duplicates kept
+            double cj = 0.0;
+            for (int x : row)
+                if (w[x] >= 0.0) cj = cj + w[x];
+            t.C[(size_t)c * g.n_str + j] = cj;
+            t.inv[(size_t)j * P + c] = cj > 0.0 ? 1.0 / cj : 0.0;
+        }
+    }
+    t.meta.assign(g.n_str, 0);
+    for (int j = 0; j < g.n_str; ++j) {
+        // the controlled slot counts as static (is_static): in an exogenous log it is a
+        // static controller's stream
+        int first = P;
+        if (!g.is_static[j]) {
+            first = 0;
+            for (int c = 0; c < P; ++c) first += lanes[c].id < g.src_id[j];
+        }
+        t.meta[j] = first | (g.csr_ptr[j + 1] > g.csr_ptr[j] ? RQ_GAME_META_EDGE : 0);
+    }
+    *out = std::move(t);
+    return RQ_OK;
+}
+
 }  // namespace rqh

@@ -59,6 +59,8 @@ class Graph:
         # src_ids of the static wall sources (run_dynamic plays their times only when
         # strictly earlier than the dynamic sources' next event, opt_model.py:289-290)
         self.static_src_ids = set()
+        # ('Opt', kw) entries of other_sources (opt_model.py:761): the players of the game
+        self.players = []
         for idx, (name, kw) in enumerate(other_sources):
             kind = _source_kind(name)
             cls = _source_class(name)
@@ -82,7 +84,13 @@ class Graph:
             if kind in (L.SRC_POISSON2, L.SRC_PWCONST) or (kind == L.SRC_REALDATA and not dyn_rd):
                 self.static_src_ids.add(int(kw["src_id"]))
             if kind == L.SRC_OPT:
-                raise NotImplementedError("an Opt broadcaster among the other sources")
+                # a competing RedQueen broadcaster: a player of the game (_run_game).  In the
+                # graph it is a replay stream -- a dynamic RealData source without times --
+                # so the stream order, and with it every log entry, is the reference's
+                self.players.append({"idx": idx, "src_id": int(kw["src_id"]),
+                                     "seed": kw.get("seed"), "q": float(kw.get("q", 1.0)),
+                                     "s": kw.get("s", 1.0)})
+                kind, dyn_rd, kw = L.SRC_REALDATA, True, {"src_id": kw["src_id"], "times": []}
             d = L.SourceDesc()
             d.kind = kind
             d.src_id = int(kw["src_id"])
@@ -190,9 +198,13 @@ class Graph:
         With a dynamic plugin among the sources, the batch's replicas (all of a batch of
         <= 64, else a seeded sample of 64) are checked to be self-driven (_verify_dynamic);
         when one reacts to other sources' events the whole batch is replayed to the
-        reactive fixed point (_run_reactive) before the result is returned."""
+        reactive fixed point (_run_reactive) before the result is returned.
+        A graph with Opt broadcasters among its other sources runs as a game (_run_game)."""
         from .opt_model import PluginReacts
         use = stream or torch.cuda.current_stream()
+        if self.players:   # Opt broadcasters among the other sources: the game
+            with torch.cuda.stream(use):
+                return self._run_game(*args, stream=use, **kw)
         with torch.cuda.stream(use):
             res = self._run(*args, stream=use, **kw)
             if any(p[4] for p in self.plugins) and not kw.get("plan_only"):
@@ -341,6 +353,225 @@ class Graph:
             return dict(zip(keys, (int(v) for v in info)))
         return self._run_loop(lib, b, keep, dev, R, Ks, n_grid, n_rep, ck, event_log,
                               gids, check, stream)
+
+    # ------------------------------------------------------------------ the game
+    @property
+    def player_ids(self):
+        """src_ids of the Opt broadcasters among the other sources (the game's players
+        besides a RedQueen controlled source), in other_sources order."""
+        return [p["src_id"] for p in self.players]
+
+    def _player_s(self, src_id, s):
+        """s over the sorted followers of ``src_id`` as the reference's Opt takes it
+        (opt_model.py:507-513): a dict by sink id, or a scalar / array times ones."""
+        fol = sorted({int(e[1]) for e in self._edges if int(e[0]) == int(src_id)})
+        if isinstance(s, dict):
+            return np.asarray([s[x] for x in fol], dtype=np.float64)
+        return np.ascontiguousarray(np.ones(len(fol), dtype=np.float64) * np.asarray(s, dtype=np.float64))
+
+    GAME_REPLAY_ROWS = 1 << 26   # dataframe rows per expand + replay chunk (40 B a row)
+    GAME_CAP_SQUEEZE = 1.0       # scales the output-log capacity down; tests only (overflow reruns)
+
+    def _game_launch(self, players, seeds, ev_t, ev_src, counts, max_events, out_cap, use):
+        """One rq_log_game: ``players`` [(src_id, q, s array)], ``seeds`` device int32
+        [R, P] (uint32 bits), the exogenous logs.  Returns (out_t, out_src, out_counts,
+        player_posts, status) device tensors."""
+        lib = L.lib()
+        dev = ev_t.device
+        R = int(counts.shape[0])
+        P = len(players)
+        arr = (L.GamePlayer * max(1, P))()
+        keep = []
+        for c, (sid, q, s) in enumerate(players):
+            sv = _arr(s, np.float64)
+            keep.append(sv)
+            arr[c].src_id, arr[c].q, arr[c].n_s = int(sid), float(q), int(sv.size)
+            arr[c].s = sv.ctypes.data_as(L._pd)
+        nbytes = C.c_size_t()
+        L.check("rq_log_game_workspace", lib.rq_log_game_workspace(self._h, P, C.byref(nbytes)))
+        ws = torch.empty(max(256, nbytes.value), dtype=torch.uint8, device=dev)
+        out_t = torch.empty((R, out_cap), dtype=torch.float64, device=dev)
+        out_src = torch.empty((R, out_cap), dtype=torch.int32, device=dev)
+        out_counts = torch.empty((R, 4), dtype=torch.int64, device=dev)
+        posts = torch.empty((R, P), dtype=torch.int64, device=dev)
+        status = torch.empty(R, dtype=torch.int32, device=dev)
+        ev_cap = int(ev_t.shape[1])
+        if ev_cap == 0:   # an empty world: nothing is read, but the pointers must be real
+            ev_t = torch.zeros((R, 1), dtype=torch.float64, device=dev)
+            ev_src = torch.zeros((R, 1), dtype=torch.int32, device=dev)
+        me = -1 if max_events is None or max_events == float("inf") else int(max_events)
+        L.check("rq_log_game", lib.rq_log_game(
+            self._h, arr, P, seeds.data_ptr(), ev_t.data_ptr(), ev_src.data_ptr(), counts.data_ptr(),
+            R, ev_cap, me, out_t.data_ptr(), out_src.data_ptr(), int(out_cap), out_counts.data_ptr(),
+            posts.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), use.cuda_stream))
+        return out_t, out_src, out_counts, posts, status
+
+    def _run_game(self, ctrl="opt", q=1.0, s=None, n_rep=1, ctrl_seed=0, world_seed=0,
+                  randomize=False, seed_mod=0, ctrl_rate=None, Ks=(1,), max_events=None,
+                  event_log=False, cap_scale=1.0, chunk=0, stream=None, check=True, sweep_mode=0,
+                  replica0=0, n_local=0, plan_only=False, s_pw=None, period=None, rep_lo=0,
+                  rep_cnt=0, rd_override=None, rd_streams=None, rep_idx=None):
+        """A batch of a graph with Opt broadcasters among its other sources.  The sources
+        no Opt influences are played by the ordinary path with their event log (ctrl
+        "wall" when the controlled source is RedQueen, which then is one more player, seeded
+        by ``ctrl_seed``); rq_log_game plays the Opts against that log, one launch per grid
+        point; metrics, counts and status come from the completed log (rq_log_expand +
+        rq_metrics_replay_batch, pandas-exact on the start-time ties every game has).  With
+        ``check`` replicas whose output log overflowed are rerun at doubled capacity
+        (``self.reruns``).  The result carries ``player_posts`` [R, P] and ``player_ids``.
+        With ``self.game_timing`` set, ``self.game_ms`` holds the device milliseconds of the
+        three stages (exogenous pass, game launches and reruns, expand + replay)."""
+        from .utils import replay_columns
+        ck = CTRL_BY_NAME[ctrl] if isinstance(ctrl, str) else int(ctrl)
+        if ck == L.SRC_OPTPW:
+            raise NotImplementedError("OptPWSignificance against Opt broadcasters among the other sources")
+        if self.plugins:
+            raise NotImplementedError("registered plugin broadcasters beside Opt broadcasters")
+        if rd_streams is not None or rd_override is not None:
+            raise NotImplementedError("rd_streams in a run with Opt broadcasters among the other sources")
+        if rep_idx is not None or replica0 or n_local or rep_lo or rep_cnt:
+            raise NotImplementedError("replica sharding (rep_idx / replica0 / n_local / rep_lo / rep_cnt) "
+                                      "of a run with Opt broadcasters among the other sources")
+        if int(sweep_mode) != 0:
+            raise NotImplementedError("sweep_mode != 0 in a run with Opt broadcasters among the other sources")
+        if plan_only:
+            raise NotImplementedError("plan_only in a run with Opt broadcasters among the other sources")
+        use = stream
+        dev = torch.device("cuda", torch.cuda.current_device())
+        qv = _arr(np.atleast_1d(q), np.float64)
+        n_grid, n_rep = qv.size, int(n_rep)
+        R = n_grid * n_rep
+        Ks = _arr(Ks, np.int32)
+        if not 1 <= Ks.size <= L.MAX_K:
+            raise ValueError("1..%d K values per run" % L.MAX_K)
+        sm = None
+        if ck == L.SRC_OPT:
+            if s is None:
+                raise ValueError("s required for the RedQueen broadcaster")
+            sm = np.asarray(s, dtype=np.float64) if (isinstance(s, np.ndarray) and s.ndim == 2) \
+                else self.s_matrix(s, n_grid)
+            if sm.shape != (n_grid, self.n_followers):
+                raise ValueError("s must be [n_grid, n_followers]")
+        # stage times for scripts/bench_game.py (game_timing): device events around the stages
+        marks = []
+
+        def mark():
+            if getattr(self, "game_timing", False):
+                ev = torch.cuda.Event(enable_timing=True)
+                ev.record(use)
+                marks.append(ev)
+        mark()
+        # 1. the exogenous world: global replica ids 0 .. R - 1, seeds as in any batch
+        exo_kw = dict(n_rep=R, world_seed=world_seed, randomize=randomize, seed_mod=seed_mod,
+                      Ks=Ks, max_events=max_events, event_log=True, cap_scale=cap_scale,
+                      chunk=chunk, stream=use, check=True)
+        if ck == L.SRC_OPT:
+            exo = self._run("wall", **exo_kw)
+        else:
+            rate = ctrl_rate
+            if ck == L.SRC_POISSON2 and ctrl_rate is not None:
+                rate = torch.as_tensor(ctrl_rate, dtype=torch.float64, device=dev).reshape(-1)
+            exo = self._run(ctrl, ctrl_seed=ctrl_seed, ctrl_rate=rate, **exo_kw)
+        reruns = int(getattr(self, "reruns", 0))
+        mark()
+        # 2. the players and their seeds (uint32 arithmetic, as the kernels' seeds wrap)
+        ids = np.arange(R, dtype=np.int64)
+        kk = ids % int(seed_mod) if int(seed_mod) > 0 else ids
+        u = (world_seed.to(torch.int64).cpu().numpy() if torch.is_tensor(world_seed)
+             else int(world_seed) + kk) & 0xFFFFFFFF
+        cols = []
+        for p in self.players:
+            if randomize:
+                cols.append((u + 99 * p["idx"]) & 0xFFFFFFFF)
+            else:
+                cols.append(np.full(R, int(p["seed"] or 0) & 0xFFFFFFFF, dtype=np.int64))
+        wall = [(p["src_id"], p["q"], self._player_s(p["src_id"], p["s"])) for p in self.players]
+        if ck == L.SRC_OPT:
+            cols.append((ctrl_seed.to(torch.int64).cpu().numpy() if torch.is_tensor(ctrl_seed)
+                         else int(ctrl_seed) + kk) & 0xFFFFFFFF)
+        seeds = torch.from_numpy(np.ascontiguousarray(
+            np.stack(cols, axis=1).astype(np.uint32).view(np.int32))).to(dev)
+        P = len(cols)
+        ev_cap = int(exo.ev_t.shape[1])
+        out_cap = max(1, int((2 * ev_cap + 64 * P) * self.GAME_CAP_SQUEEZE))
+        if max_events is not None and max_events != float("inf"):
+            out_cap = max(1, min(out_cap, int(max_events)))
+        parts = []
+        mark()
+        for g in range(n_grid):
+            players = list(wall)
+            if ck == L.SRC_OPT:
+                players.append((self.src_id, float(qv[g]), sm[g]))
+            lo, hi = g * n_rep, (g + 1) * n_rep
+            parts.append(self._game_launch(players, seeds[lo:hi], exo.ev_t[lo:hi], exo.ev_src[lo:hi],
+                                           exo.counts[lo:hi], max_events, out_cap, use))
+        out_t, out_src, out_counts, posts, status = (torch.cat([p[k] for p in parts]) for k in range(5))
+        # overflowed output logs again, alone, at doubled capacity
+        while check:
+            use.synchronize()
+            flagged = np.flatnonzero(status.cpu().numpy() & L.ST_ROWS_OVERFLOW)
+            if not flagged.size:
+                break
+            if out_cap > (1 << 28):
+                raise L.RQError("rq_log_game", L.RQ_EOVERFLOW)
+            out_cap *= 2
+            at = torch.from_numpy(flagged).to(dev)
+            t2 = torch.empty((R, out_cap), dtype=out_t.dtype, device=dev)
+            s2 = torch.empty((R, out_cap), dtype=out_src.dtype, device=dev)
+            t2[:, :out_t.shape[1]] = out_t
+            s2[:, :out_src.shape[1]] = out_src
+            out_t, out_src = t2, s2
+            for g in np.unique(flagged // n_rep):
+                pick = flagged[flagged // n_rep == g]
+                pk = torch.from_numpy(pick).to(dev)
+                players = list(wall)
+                if ck == L.SRC_OPT:
+                    players.append((self.src_id, float(qv[g]), sm[g]))
+                r = self._game_launch(players, seeds[pk].contiguous(), exo.ev_t[pk].contiguous(),
+                                      exo.ev_src[pk].contiguous(), exo.counts[pk].contiguous(),
+                                      max_events, out_cap, use)
+                out_t[pk], out_src[pk] = r[0], r[1]
+                out_counts[pk], posts[pk], status[pk] = r[2], r[3], r[4]
+            reruns += int(at.numel())
+        self.reruns = reruns
+        mark()
+        # 3. metrics and counts of the completed log: its dataframe rows through the replay
+        metrics = torch.empty((R, Ks.size + 2), dtype=torch.float64, device=dev)
+        counts = out_counts.clone()
+        res = BatchResult(self, metrics, counts, status, out_t, out_src, Ks, n_grid, n_rep)
+        lo = 0
+        row_all = torch.empty(R + 1, dtype=torch.int64, device=dev)
+        L.check("rq_log_rows", L.lib().rq_log_rows(self._h, out_src.data_ptr(), out_counts.data_ptr(), R,
+                                                   int(out_src.shape[1]), row_all.data_ptr(), use.cuda_stream))
+        ra = row_all.cpu().numpy()
+        while lo < R:   # replica chunks of at most GAME_REPLAY_ROWS dataframe rows (one at least)
+            hi = int(np.searchsorted(ra, ra[lo] + self.GAME_REPLAY_ROWS, side="right")) - 1
+            hi = min(R, max(hi, lo + 1))
+            sub = BatchResult(self, metrics[lo:hi], out_counts[lo:hi], status[lo:hi], out_t[lo:hi],
+                              out_src[lo:hi], Ks, 1, hi - lo)
+            ro, c = sub._log_columns(use)
+            if int(ro[-1]) == 0:   # no event of the chunk has an edge: empty dataframes
+                metrics[lo:hi] = float("nan")
+                lo = hi
+                continue
+            off = torch.from_numpy(np.ascontiguousarray(ro)).to(dev)
+            m, cn = replay_columns(c["t"], c["src_id"], c["sink_id"], c["event_id"], off, self.src_id,
+                                   self.end_time, Ks)
+            metrics[lo:hi] = m
+            counts[lo:hi, 0], counts[lo:hi, 1], counts[lo:hi, 3] = cn[:, 0], cn[:, 1], cn[:, 2]
+            lo = hi
+        mark()
+        if marks:
+            marks[-1].synchronize()
+            self.game_ms = {"exogenous": marks[0].elapsed_time(marks[1]), "game": marks[2].elapsed_time(marks[3]),
+                            "replay": marks[3].elapsed_time(marks[4])}
+        if not event_log:
+            res.ev_t = res.ev_src = None
+        res.player_posts = posts
+        res.player_ids = [p[0] for p in wall] + ([self.src_id] if ck == L.SRC_OPT else [])
+        res.replica0 = 0
+        res.global_ids = ids
+        return res
 
     def _launch(self, lib, b, dev, R, Ks, n_grid, n_rep, event_log, use):
         """One rq_run_batch of R output replicas on stream ``use``.  The outputs (and the

@@ -547,10 +547,10 @@ class Manager:
                                                                        PiecewiseConst, RealData)):
                     ctrl = s
         if ctrl is None:
+            # one RedQueen broadcaster without a controlled slot takes it; several play each
+            # other as the game's players (engine.Graph._run_game) beside an empty slot
             opts = [s for s in self.sources if isinstance(s, (Opt, OptPWSignificance))]
-            if len(opts) > 1:
-                raise NotImplementedError("more than one Opt broadcaster in one run")
-            ctrl = opts[0] if opts else None
+            ctrl = opts[0] if len(opts) == 1 else None
         return ctrl
 
     def run_dynamic(self, max_events=float('inf')):
@@ -563,9 +563,8 @@ class Manager:
         ctrl = self._controlled()
         others = [s for s in self.sources if s is not ctrl]
         for s in others:
-            if s._rq_kind in (L.SRC_OPT, L.SRC_OPTPW):
-                raise NotImplementedError("broadcaster %s has no engine kernel" %
-                                          type(s).__name__)
+            if s._rq_kind == L.SRC_OPTPW:
+                raise NotImplementedError("OptPWSignificance among the other sources has no engine kernel")
         if ctrl is None:
             ids = [s.src_id for s in self.sources] + [e[0] for e in self.edge_list]
             ctrl_id = min(ids) - 1
@@ -578,6 +577,9 @@ class Manager:
         probes = []
         other_desc = []
         for s in others:
+            if s._rq_kind == L.SRC_OPT:   # a competing RedQueen broadcaster: a player of the game
+                other_desc.append(("Opt", {"src_id": s.src_id, "seed": s.seed, "q": s.q, "s": s.s}))
+                continue
             if s._rq_kind is not None:
                 other_desc.append((type(s).__name__, s._kwargs()))
                 continue
