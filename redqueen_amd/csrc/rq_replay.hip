@@ -276,7 +276,15 @@ __device__ __forceinline__ void rp_fast_body(RpArgs a)
     //       [5] own events, [6] world events, [7] key dump cursor, [8] bucket allocator,
     //       [9] table full (a batch's new sinks found no empty slot: this tier gives up)
     if (tid < 16) misc[tid] = 0;
-    if (TIER == a.first_tier && tid == 0) inf->flags = 0;   // this call's status (the first pass)
+    if (TIER == a.first_tier && tid == 0) {   // this call's status (the first pass)
+        inf->flags = 0;
+        // a dataframe every tier gives up (RQ_EOVERFLOW) reports these as they stand: the
+        // host never clears the workspace
+        inf->n_piv = 0;
+        inf->n_own = 0;
+        inf->n_world = 0;
+        inf->S = 0;
+    }
     for (int64_t h = tid; h <= tcap; h += RP_B) {
         tkeys[h] = RP_EMPTY_KEY;
         tst[h] = RpSlot{0, 0, -1, 0};

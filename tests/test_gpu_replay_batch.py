@@ -8,12 +8,14 @@ tests/test_oracle.py) where a case has no fixture, and -- at full C3 size -- the
 engine's own fused metrics, which must equal a replay of the dataframe it exports.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 import pandas as pd
 import pytest
 
 from redqueen_amd import graphs
+from tests.replay_cases import random_df
 
 pytestmark = pytest.mark.gpu
 KS = [1, 2, 5, 10]
@@ -133,17 +135,8 @@ def test_batch_adversarial_and_fractional(golden):
         assert res.sinks[i] == df.sink_id.nunique()
 
 
-def _random_df(rs, n_events, sinks, dup_p=0.0, tie_p=0.0, own_p=0.2):
-    rows, t = [], 0.0
-    for e in range(n_events):
-        if rs.rand() >= tie_p:
-            t += float(rs.exponential(0.1))
-        src = 1 if rs.rand() < own_p else int(rs.randint(2, 9))
-        ss = list(rs.choice(sinks, rs.randint(1, 40), replace=False))
-        if rs.rand() < dup_p:
-            ss.append(ss[0])
-        rows += [(100 + e, src, t, int(y)) for y in ss]
-    return pd.DataFrame.from_records(rows, columns=["event_id", "src_id", "t", "sink_id"])
+# the shared builder (tests/replay_cases.py) at this file's event widths, 1..39
+_random_df = functools.partial(random_df, max_width=39)
 
 
 @pytest.mark.parametrize("dup_p,tie_p", [(0.0, 0.0), (0.05, 0.3)])

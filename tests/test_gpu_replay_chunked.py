@@ -15,6 +15,7 @@ import pandas as pd
 import pytest
 
 from redqueen_amd import graphs
+from tests.replay_cases import random_df as _random_df
 from tests.test_gpu_replay_batch import KS, _ctx, _readme_df
 
 pytestmark = pytest.mark.gpu
@@ -37,22 +38,6 @@ def _replay(torch, U, df, src_id, end, chunked, Ks=KS):
         else:
             os.environ["RQ_RP_CHUNK"] = old
     return m[0].cpu().numpy(), c[0].cpu().numpy()
-
-
-def _random_df(rs, n_events, sinks, dup_p=0.0, tie_p=0.0, own_p=0.2):
-    """Events of 1..min(40, #sinks) distinct sinks (+ a duplicated sink row with
-    probability dup_p), equal times with probability tie_p, own posts own_p."""
-    rows, t = [], 0.0
-    hi = min(40, len(sinks)) + 1
-    for e in range(n_events):
-        if rs.rand() >= tie_p:
-            t += float(rs.exponential(0.1))
-        src = 1 if rs.rand() < own_p else int(rs.randint(2, 9))
-        ss = list(rs.choice(sinks, rs.randint(1, hi), replace=False))
-        if rs.rand() < dup_p:
-            ss.append(ss[0])
-        rows += [(100 + e, src, t, int(y)) for y in ss]
-    return pd.DataFrame.from_records(rows, columns=["event_id", "src_id", "t", "sink_id"])
 
 
 def _oracle(O, df, src_id, end, Ks=KS):
