@@ -44,6 +44,10 @@
  *                       the seen sink-time per rank value and time bin
  *                       utils.py:38-56, :84-98 (opt_runs.py:31-33's Ks curve)
  *                       for every replica of an RQ_RUN_EVENT_LOG batch at once
+ *   rq_log_metrics      utils.rank_of_src_in_df + time_in_top_k / average_rank /
+ *                       int_r_2 / num_tweets_of over the whole horizon, exact on
+ *                       equal times                          utils.py:38-56, :84-121, :170-176
+ *                       for every replica of a batch of event logs at once
  *   rq_log_game         Opt broadcasters among SimOpts.other_sources  opt_model.py:761,
  *                       each Opt.get_next_interval :502-544 in run_dynamic's loop :271-309
  *
@@ -568,6 +572,57 @@ int rq_log_rank_hist(rq_graph_t g, const double* ev_t, const int32_t* ev_src,
                      int32_t* max_rank,   /* device [n_rep] */
                      int32_t* status,     /* device [n_rep] */
                      void* hip_stream);
+
+/* Whole-horizon metrics of a batch's event logs, exact on equal times: time_in_top_k,
+ * average_rank and int_r_2 (utils.py:84-121) over rank_of_src_in_df's pivot table
+ * (utils.py:38-56) and num_tweets_of's counts (utils.py:170-176), bit for bit what
+ * rq_metrics_replay_batch gives on the logs' dataframe rows (rq_log_expand), without
+ * writing a row.  Logs, counts[i][2] clamping, stream indices outside the graph, the rank
+ * rule and Ks are rq_log_timeline's.
+ *   A t-group is the maximal run of consecutive events with equal t.  Its pivot row is
+ * made when some event of it has an edge.  The group's cell of a sink x it touches is
+ * (double)(sum of the ranks of x's rows in the group) / (double)(their number) -- pandas'
+ * pivot mean; an untouched sink keeps its cell (ffill), while its rank runs on from the
+ * last rank.  The row holds nvalid (sinks with a cell), c_K (cells <= K-1) and rowsum: the
+ * exact integer sum while every cell is integral, else numpy's pairwise sum over the
+ * replica's pivot columns -- the S sinks that get a row anywhere in the replica, in
+ * ascending sink id, a column without a cell yet counting 0.  (A graph sink the replica
+ * never reaches is no column: a zero there would shift numpy's tree and the rounding.)
+ *   metrics[i] = numpy's sums (8192-row chunks, pairwise inside) of ((double)c_K / S) * dt,
+ * m * dt and (m * m) * dt over the rows, m = rowsum / (double)nvalid, dt to the next row,
+ * the last to the graph's end_time; every product rounded.  out_counts[i] is the replay's
+ * layout: [0] the controlled stream's events with an edge, [1] the other streams', [2]
+ * pivot rows, [3] S.
+ *   status[i]: 0; RQ_ST_TIE when some sink got two rows in one t-group (informational: the
+ * values are exact, as in the sequential sweep); RQ_ST_EMPTY when no event had an edge
+ * (metrics NaN, counts 0).  No replica's output depends on its neighbours or on the
+ * launch; every output element is written once (no atomics on outputs, no zeroing pass).
+ *   workspace: device, 8-byte aligned, at least rq_log_metrics_workspace's bytes: a block's
+ * pivot rows before the same wave integrates them.  It grows with ev_cap and with n_rep up
+ * to 4096 replicas.  Non-decreasing t is the caller's contract; nothing is accessed out of
+ * bounds whatever the arrays hold.  Enqueues on hip_stream only.
+ *   RQ_EINVAL: a null pointer, n_rep < 1 (or > INT32_MAX), ev_cap < 1, bad nK or K, a
+ * workspace too small or misaligned.  RQ_EUNSUPPORTED, nothing launched (the workspace query
+ * answers the same): ev_cap > 2^20 (a sink's rows in one t-group are counted in 24 bits and
+ * their ranks summed in 40; rq_log_expand + rq_metrics_replay_batch take such logs), a graph with
+ * duplicate edges, or with more than RQ_LOG_METRICS_MAX_SINKS sinks.  A sink's state is 16
+ * bytes of the workgroup's 160 KiB LDS (rank, t-group tag, and the group's row count and
+ * rank sum packed in 64 bits -- one 128-bit LDS read and write per row); beside it stand
+ * 4,784 bytes of summation scratch and 6 bytes per 32 sinks of column index, which leaves
+ * room for 9,825 sinks: the limit is 9,800.  (The pass that finds a replica's columns
+ * keeps one bit per stream in the same LDS; a graph of more than ~1.2 million streams is
+ * refused too.)
+ *   Added without an ABI version change (RQ_ABI_VERSION stays 6); a caller detects the
+ * functions by their symbols. */
+#define RQ_LOG_METRICS_MAX_SINKS 9800
+int rq_log_metrics_workspace(rq_graph_t g, int64_t n_rep, int64_t ev_cap, int32_t nK, size_t* bytes);
+int rq_log_metrics(rq_graph_t g, const double* ev_t, const int32_t* ev_src,
+                   const int64_t* counts, int64_t n_rep, int64_t ev_cap,
+                   const int32_t* Ks, int32_t nK,   /* host, 1 <= nK <= 4, K >= 1 */
+                   double* metrics,       /* device [n_rep][nK + 2]: top_K..., avg_rank, r_2 */
+                   int64_t* out_counts,   /* device [n_rep][4] */
+                   int32_t* status,       /* device [n_rep] */
+                   void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /* Competing RedQueen broadcasters (Opt among SimOpts.other_sources, opt_model.py:493-544,
  * :761): several Opts -- the PLAYERS -- post against each other and against an exogenous

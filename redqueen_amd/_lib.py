@@ -69,6 +69,7 @@ MAX_RD = 64
 TIMELINE_MAX_SINKS = 12288   # RQ_TIMELINE_MAX_SINKS
 FOLLOWERS_TILED_MAX_SINKS = 40960   # RQ_FOLLOWERS_TILED_MAX_SINKS
 RANK_HIST_MAX_RANKS = 255    # RQ_RANK_HIST_MAX_RANKS
+LOG_METRICS_MAX_SINKS = 9800   # RQ_LOG_METRICS_MAX_SINKS
 
 _P = C.c_void_p
 _pd = C.POINTER(C.c_double)
@@ -185,6 +186,11 @@ def lib():
     L.rq_log_game.argtypes = [_P, C.POINTER(GamePlayer), C.c_int32, _P, _P, _P, _P, C.c_int64,
                               C.c_int64, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_size_t, _P]
     L.rq_log_game.restype = C.c_int
+    L.rq_log_metrics_workspace.argtypes = [_P, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]
+    L.rq_log_metrics_workspace.restype = C.c_int
+    L.rq_log_metrics.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int64, _pi32, C.c_int32, _P, _P, _P, _P,
+                                 C.c_size_t, _P]
+    L.rq_log_metrics.restype = C.c_int
     L.rq_timing.argtypes = [C.c_int]
     L.rq_timing_read.argtypes = [_pd, _pi64]
     for fn in ("rq_timing", "rq_timing_read", "rq_graph_build", "rq_graph_free", "rq_graph_info", "rq_graph_source_ids",
@@ -241,6 +247,7 @@ EXPORTED = ["rq_abi_version", "rq_strerror", "rq_graph_build", "rq_graph_free", 
             "rq_metrics_replay", "rq_metrics_replay_batch", "rq_oracle_workspace_size", "rq_oracle_dp", "rq_rank_table",
             "rq_u_int", "rq_log_rows", "rq_log_expand", "rq_log_timeline", "rq_log_followers",
             "rq_log_followers_tiled_workspace", "rq_log_followers_tiled",
-            "rq_log_rank_hist", "rq_log_game_workspace", "rq_log_game", "rq_timing", "rq_timing_read"]
+            "rq_log_rank_hist", "rq_log_metrics_workspace", "rq_log_metrics", "rq_log_game_workspace", "rq_log_game",
+            "rq_timing", "rq_timing_read"]
 # rq_log_followers_max_sinks, rq_log_followers_tile_sinks and rq_log_game_table_in_lds return
 # int32_t, no status

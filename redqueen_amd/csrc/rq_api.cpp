@@ -1224,6 +1224,58 @@ int rq_log_rank_hist(rq_graph_t g, const double* ev_t, const int32_t* ev_src, co
     return rq_launch_rank_hist(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
 }
 
+// the blocks of an rq_log_metrics launch: one per replica up to RQ_LM_SLOTS
+static int64_t log_metrics_slots(int64_t n_rep) { return n_rep < RQ_LM_SLOTS ? n_rep : RQ_LM_SLOTS; }
+
+// what rq_log_metrics and its workspace query refuse alike
+static int log_metrics_check(rq_graph_t g, int64_t n_rep, int64_t ev_cap, int32_t nK)
+{
+    if (!g || n_rep < 1 || n_rep > INT32_MAX || ev_cap < 1) return RQ_EINVAL;
+    if (nK < 1 || nK > RQ_MAX_K) return RQ_EINVAL;
+    if (log_unsupported(g, RQ_LOG_METRICS_MAX_SINKS)) return RQ_EUNSUPPORTED;
+    // a cell counts a column's rows in a t-group in 24 bits and sums their ranks in 40: logs
+    // with room for more events are not played here (the dataframe replay takes any)
+    if (ev_cap > RQ_LM_MAX_EV_CAP) return RQ_EUNSUPPORTED;
+    // the stream bits share the cells' LDS: past ~1.2 million streams they outgrow it
+    if (rq_log_metrics_lds_bytes(g->n_sinks, g->n_str) > RQ_LM_LDS_BYTES) return RQ_EUNSUPPORTED;
+    return RQ_OK;
+}
+
+int rq_log_metrics_workspace(rq_graph_t g, int64_t n_rep, int64_t ev_cap, int32_t nK, size_t* bytes)
+{
+    if (!bytes) return RQ_EINVAL;
+    const int rc = log_metrics_check(g, n_rep, ev_cap, nK);
+    if (rc != RQ_OK) return rc;
+    *bytes = (size_t)log_metrics_slots(n_rep) * rq_log_metrics_slot_bytes(ev_cap, nK);
+    return RQ_OK;
+}
+
+int rq_log_metrics(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const int64_t* counts,
+                   int64_t n_rep, int64_t ev_cap, const int32_t* Ks, int32_t nK, double* metrics,
+                   int64_t* out_counts, int32_t* status, void* workspace, size_t workspace_bytes,
+                   void* hip_stream)
+{
+    if (!g || !ev_t || !ev_src || !counts || !metrics || !out_counts || !status || !workspace) return RQ_EINVAL;
+    LogMetricsArgs a{};
+    if (!copy_ks(Ks, nK, a.Ks)) return RQ_EINVAL;
+    const int rc = log_metrics_check(g, n_rep, ev_cap, nK);
+    if (rc != RQ_OK) return rc;
+    a.n_slots = (int)log_metrics_slots(n_rep);
+    a.slot_bytes = rq_log_metrics_slot_bytes(ev_cap, nK);
+    if (workspace_bytes < (size_t)a.n_slots * a.slot_bytes || (reinterpret_cast<uintptr_t>(workspace) & 7))
+        return RQ_EINVAL;
+    a.log = log_view(g, ev_t, ev_src, counts, n_rep, ev_cap);
+    a.nK = nK;
+    a.state_bytes = rq_log_metrics_state_bytes(g->n_sinks, g->n_str);
+    a.rows = static_cast<char*>(workspace);
+    a.metrics = metrics;
+    a.out_counts = out_counts;
+    a.status = status;
+    hipStream_t st = (hipStream_t)hip_stream;
+    TimedLaunch tl(K_REPLAY, st);
+    return rq_launch_log_metrics(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
+}
+
 int rq_log_game_workspace(rq_graph_t g, int32_t n_players, size_t* bytes)
 {
     if (!g || !bytes || n_players < 1) return RQ_EINVAL;

@@ -435,6 +435,48 @@ struct RankHistArgs {
 };
 hipError_t rq_launch_rank_hist(const RankHistArgs& a, hipStream_t s);
 
+// ---- whole-horizon metrics from event logs, exact on ties (rq_log_metrics.hip) ----
+constexpr int RQ_LM_NL = 66;                // leaf capacity of the scan's LDS layout (as RQ_FWS_NL)
+constexpr size_t RQ_LM_SCRATCH_BYTES = 4784;   // 8 * npsum_lds_doubles<RQ_MAX_K + 2, 66>() >= wave_npsum<1>'s 4128
+constexpr int RQ_LM_CELL_BYTES = 16;        // one pivot column's state
+constexpr size_t RQ_LM_LDS_BYTES = 160 * 1024;   // one workgroup's LDS on gfx950
+// blocks of a launch, each with its own rows in the workspace.  Blocks stride over the
+// replicas, so fewer would do, but the stride is static: at 2048 the C3 game's 10,000 logs
+// took 59-68 ms against 45-51 ms at 4096 (more, shorter blocks even out)
+constexpr int RQ_LM_SLOTS = 4096;
+constexpr int64_t RQ_LM_MAX_EV_CAP = 1 << 20;   // a column's rows in a t-group in 24 bits, their rank sum in 40
+// bytes of the per-column state: the cells, or the stream bits the first step keeps there
+inline size_t rq_log_metrics_state_bytes(int n_sinks, int n_str)
+{
+    const size_t cells = (size_t)n_sinks * RQ_LM_CELL_BYTES;
+    const size_t sbits = (((size_t)n_str + 31) / 32 * 4 + 15) / 16 * 16;
+    return cells > sbits ? cells : sbits;
+}
+// scratch + state + one bit per sink + a uint16 per word of those bits
+inline size_t rq_log_metrics_lds_bytes(int n_sinks, int n_str)
+{
+    const size_t W = ((size_t)n_sinks + 31) / 32;
+    return RQ_LM_SCRATCH_BYTES + rq_log_metrics_state_bytes(n_sinks, n_str) + 4 * W + (2 * W + 3) / 4 * 4;
+}
+// one block's rows: t f64, rowsum f64, nvalid u32, c_K u32 x nK for up to ev_cap rows
+inline size_t rq_log_metrics_slot_bytes(int64_t ev_cap, int nK)
+{
+    return ((size_t)ev_cap * (20 + 4 * (size_t)nK) + 15) / 16 * 16;
+}
+struct LogMetricsArgs {
+    LogView log;
+    int Ks[RQ_MAX_K];
+    int nK;
+    int n_slots;              // blocks; block b plays replicas b, b + n_slots, ...
+    size_t state_bytes;       // rq_log_metrics_state_bytes
+    size_t slot_bytes;        // rq_log_metrics_slot_bytes
+    char* rows;               // workspace [n_slots][slot_bytes]
+    double* metrics;          // [n_rep][nK + 2]
+    int64_t* out_counts;      // [n_rep][4]
+    int32_t* status;          // [n_rep]
+};
+hipError_t rq_launch_log_metrics(const LogMetricsArgs& a, hipStream_t s);
+
 // ---- competing RedQueen broadcasters against an exogenous log (rq_game.hip) ----
 struct GameArgs {
     const double* ev_t;       // [n_rep][ev_cap] the exogenous logs

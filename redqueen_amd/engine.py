@@ -371,6 +371,10 @@ class Graph:
 
     GAME_REPLAY_ROWS = 1 << 26   # dataframe rows per expand + replay chunk (40 B a row)
     GAME_CAP_SQUEEZE = 1.0       # scales the output-log capacity down; tests only (overflow reruns)
+    # stage 3 of a game: "log" = rq_log_metrics on the completed log (a graph or a log capacity
+    # it refuses takes the other route), "replay" = rq_log_expand + rq_metrics_replay_batch; the
+    # same bits, C3 with 10,000 replicas in 45-52 ms against 3,053-3,920 ms (profiles/game_c3_logmetrics.json)
+    GAME_METRICS = "log"
 
     def _game_launch(self, players, seeds, ev_t, ev_src, counts, max_events, out_cap, use):
         """One rq_log_game: ``players`` [(src_id, q, s array)], ``seeds`` device int32
@@ -415,12 +419,14 @@ class Graph:
         no Opt influences are played by the ordinary path with their event log (ctrl
         "wall" when the controlled source is RedQueen, which then is one more player, seeded
         by ``ctrl_seed``); rq_log_game plays the Opts against that log, one launch per grid
-        point; metrics, counts and status come from the completed log (rq_log_expand +
-        rq_metrics_replay_batch, pandas-exact on the start-time ties every game has).  With
-        ``check`` replicas whose output log overflowed are rerun at doubled capacity
+        point; metrics and counts come from the completed log, pandas-exact on the
+        start-time ties every game has: by rq_log_metrics (``GAME_METRICS`` "log"; a graph or
+        a log capacity above 2^20 events, which it refuses, takes the other route) or by
+        rq_log_expand + rq_metrics_replay_batch ("replay"), the same bits.  With ``check`` replicas whose output log overflowed are rerun at doubled capacity
         (``self.reruns``).  The result carries ``player_posts`` [R, P] and ``player_ids``.
         With ``self.game_timing`` set, ``self.game_ms`` holds the device milliseconds of the
-        three stages (exogenous pass, game launches and reruns, expand + replay)."""
+        three stages (exogenous pass, game launches and reruns, and under the key "replay"
+        the metrics of the completed log on either route)."""
         from .utils import replay_columns
         ck = CTRL_BY_NAME[ctrl] if isinstance(ctrl, str) else int(ctrl)
         if ck == L.SRC_OPTPW:
@@ -535,15 +541,33 @@ class Graph:
             reruns += int(at.numel())
         self.reruns = reruns
         mark()
-        # 3. metrics and counts of the completed log: its dataframe rows through the replay
+        # 3. metrics and counts of the completed log: straight from it, or its dataframe rows
+        # through the replay
         metrics = torch.empty((R, Ks.size + 2), dtype=torch.float64, device=dev)
         counts = out_counts.clone()
         res = BatchResult(self, metrics, counts, status, out_t, out_src, Ks, n_grid, n_rep)
+        if self.GAME_METRICS not in ("log", "replay"):
+            raise ValueError("Graph.GAME_METRICS: 'log' or 'replay' expected")
+        lm = None
+        if self.GAME_METRICS == "log":   # straight from the log, where graph and capacity are supported
+            try:
+                lm = BatchResult(self, None, out_counts, None, out_t, out_src, Ks, n_grid, n_rep)._log_metrics(Ks, use)
+            except L.RQError as e:
+                if e.code != L.RQ_EUNSUPPORTED:
+                    raise
         lo = 0
-        row_all = torch.empty(R + 1, dtype=torch.int64, device=dev)
-        L.check("rq_log_rows", L.lib().rq_log_rows(self._h, out_src.data_ptr(), out_counts.data_ptr(), R,
-                                                   int(out_src.shape[1]), row_all.data_ptr(), use.cuda_stream))
-        ra = row_all.cpu().numpy()
+        if lm is not None:
+            metrics.copy_(lm.metrics)
+            # a batch in which no event has an edge keeps the game kernel's counts, as the
+            # other route's empty chunk does
+            if bool((lm.counts[:, 3] > 0).any().item()):
+                counts[:, 0], counts[:, 1], counts[:, 3] = lm.counts[:, 0], lm.counts[:, 1], lm.counts[:, 2]
+            lo = R
+        else:
+            row_all = torch.empty(R + 1, dtype=torch.int64, device=dev)
+            L.check("rq_log_rows", L.lib().rq_log_rows(self._h, out_src.data_ptr(), out_counts.data_ptr(), R,
+                                                       int(out_src.shape[1]), row_all.data_ptr(), use.cuda_stream))
+            ra = row_all.cpu().numpy()
         while lo < R:   # replica chunks of at most GAME_REPLAY_ROWS dataframe rows (one at least)
             hi = int(np.searchsorted(ra, ra[lo] + self.GAME_REPLAY_ROWS, side="right")) - 1
             hi = min(R, max(hi, lo + 1))
@@ -1087,12 +1111,86 @@ class BatchResult:
                 status.data_ptr(), use.cuda_stream))
         return RankHist(e, nr, hist, n_seen, max_rank, status)
 
+    LOG_METRICS_WS_BYTES = 1 << 31   # workspace budget of one rq_log_metrics call
+
+    def log_metrics(self, Ks=None, stream=None):
+        """The whole-horizon metrics and counts straight from the event logs, exact on
+        equal times (rq_log_metrics): what rq_metrics_replay_batch gives on the logs'
+        dataframe rows, bit for bit, without a dataframe.  ``Ks``: default the result's
+        own.  Returns a ``LogMetrics`` of device tensors: ``metrics`` [R, nK + 2],
+        ``counts`` [R, 4] (own events, other events, pivot rows, pivot columns) and
+        ``status`` [R] (ST_TIE is informational, ST_EMPTY replicas are NaN).  Replicas go
+        in chunks that keep the workspace within LOG_METRICS_WS_BYTES.  Raises
+        RQError(RQ_EUNSUPPORTED) for a graph with duplicate edges or more than
+        LOG_METRICS_MAX_SINKS sinks, and for logs with room for more than 2^20 events per
+        replica (``ev_t.shape[1]``; ``utils.replay_columns`` over ``log_columns()`` takes
+        those); needs event_log=True."""
+        self._log_graph()
+        ks = self._log_ks(Ks)
+        use = stream or torch.cuda.current_stream()
+        with torch.cuda.stream(use):
+            return self._log_metrics(ks, use)
+
+    def _log_metrics(self, ks, use):
+        g, lib = self.graph, L.lib()
+        dev = self.ev_t.device
+        R, cap = self.ev_t.shape
+        metrics = torch.empty((R, ks.size + 2), dtype=torch.float64, device=dev)
+        counts = torch.empty((R, 4), dtype=torch.int64, device=dev)
+        status = torch.empty(R, dtype=torch.int32, device=dev)
+        nb = C.c_size_t()
+        if R == 0 or cap == 0:   # nothing to play: every replica is empty
+            L.check("rq_log_metrics_workspace", lib.rq_log_metrics_workspace(g._h, 1, 1, ks.size, C.byref(nb)))
+            metrics.fill_(float("nan"))
+            counts.zero_()
+            status.fill_(L.ST_EMPTY)
+            return LogMetrics([int(k) for k in ks], metrics, counts, status)
+        # the whole batch in one launch if its workspace (which stops growing at a fixed
+        # number of blocks) fits the budget, else as many replicas a call as fit it
+        chunk = R
+        L.check("rq_log_metrics_workspace", lib.rq_log_metrics_workspace(g._h, R, cap, ks.size, C.byref(nb)))
+        if nb.value > self.LOG_METRICS_WS_BYTES:
+            L.check("rq_log_metrics_workspace", lib.rq_log_metrics_workspace(g._h, 1, cap, ks.size, C.byref(nb)))
+            chunk = max(1, min(R, self.LOG_METRICS_WS_BYTES // nb.value))
+            L.check("rq_log_metrics_workspace",
+                    lib.rq_log_metrics_workspace(g._h, chunk, cap, ks.size, C.byref(nb)))
+        ws = torch.empty(max(256, nb.value), dtype=torch.uint8, device=dev)
+        for lo in range(0, R, chunk):
+            n = min(chunk, R - lo)
+            L.check("rq_log_metrics", lib.rq_log_metrics(
+                g._h, self.ev_t[lo:].data_ptr(), self.ev_src[lo:].data_ptr(), self.counts[lo:].data_ptr(),
+                n, cap, ks.ctypes.data_as(L._pi32), ks.size, metrics[lo:].data_ptr(),
+                counts[lo:].data_ptr(), status[lo:].data_ptr(), ws.data_ptr(), ws.numel(),
+                use.cuda_stream))   # ws: allocated on `use`, reused there only
+        return LogMetrics([int(k) for k in ks], metrics, counts, status)
+
     def events(self, i):
         """(t, src_id) numpy arrays of replica i (needs event_log=True)."""
         n = int(self.counts[i, 2].item())
         t = self.ev_t[i, :n].cpu().numpy()
         s = self.graph.stream_src_ids[self.ev_src[i, :n].cpu().numpy()]
         return t, s
+
+
+class LogMetrics:
+    """BatchResult.log_metrics' outputs: ``metrics`` [R, nK + 2] (top_K..., avg_rank,
+    r_2), ``counts`` [R, 4] (the controlled source's events with an edge, the others',
+    pivot rows, pivot columns) and ``status`` [R] (0, ST_TIE: informational, or ST_EMPTY:
+    metrics NaN), device tensors."""
+
+    def __init__(self, Ks, metrics, counts, status):
+        self.Ks, self.metrics, self.counts, self.status = Ks, metrics, counts, status
+
+    def top_k(self, k):
+        return self.metrics[:, self.Ks.index(k)]
+
+    @property
+    def avg_rank(self):
+        return self.metrics[:, len(self.Ks)]
+
+    @property
+    def r_2(self):
+        return self.metrics[:, len(self.Ks) + 1]
 
 
 class Timeline:
