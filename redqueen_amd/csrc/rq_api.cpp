@@ -549,7 +549,7 @@ SweepArgs sweep_args(const rq_graph* g, const Plan& p, const rq_batch_desc* b, c
     sa.fw_hfill = p.fw_h;
     if (kn.fw_hfill.set) sa.fw_hfill = std::max(1, std::min(p.gwin, kn.fw_hfill.v));   // tuning only
 #ifdef RQ_PHASE_CLOCK
-    sa.clk = phase_clk();
+    if (!kn.clk_merge) sa.clk = phase_clk();   // RQ_CLK_MERGE: the eight sums are the merge's alone
 #endif
     sa.lds_total = p.g_total;
     sa.metrics = out->metrics;

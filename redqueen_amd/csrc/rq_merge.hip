@@ -475,6 +475,13 @@ __global__ __launch_bounds__(MG_B) void rq_merge_streams(MergeArgs a)
 // than FCAP arrivals at ONE time are emitted FCAP at a time in (stream, position) order
 // and flagged, as there with MG_CAP.
 // ---------------------------------------------------------------------------
+#ifndef RQ_FLAT_BT
+#define RQ_FLAT_BT 7   // pre-pass chunks in flight per lane: 56 arrivals of a stream (two lanes) per round trip
+#endif
+#ifndef RQ_FLAT_NB
+#define RQ_FLAT_NB 16   // slices of the table (16 / 32 / 64 measured)
+#endif
+
 // sub_of, kept inside the counts whatever the input (an unsorted stream's t < t_lo)
 template <int M>
 __device__ __forceinline__ int flat_sub(double t, double t_lo, double scale)
@@ -483,7 +490,33 @@ __device__ __forceinline__ int flat_sub(double t, double t_lo, double scale)
     return sb > 0 ? sb : 0;
 }
 
-template <int FB, int FCAP, int FT8>
+// the neighbour lane's value (lanes 2 i and 2 i + 1 swap: quad_perm [1,0,3,2])
+__device__ __forceinline__ uint32_t flat_swap1(uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);
+}
+__device__ __forceinline__ double flat_swap1_f64(double x)
+{
+    const uint64_t b = (uint64_t)__double_as_longlong(x);
+    return __longlong_as_double((long long)(((uint64_t)flat_swap1((uint32_t)(b >> 32)) << 32) | flat_swap1((uint32_t)b)));
+}
+
+// NB > 0: windows from a slice table.  A pre-pass reads every stream once, front
+// to back, with loads whose addresses depend on st_off / slen alone, and counts per stream s
+// and slice b of NB equal slices of [t_min, end] the arrivals before slice b (cum, packed
+// 16-bit in the registers of the stream's two lanes) and their totals over the streams (tot,
+// LDS).  A window is then the longest run of whole slices from the current one that holds
+// <= FCAP arrivals: its runs are cum differences, so no load decides where a run ends.
+// An arrival's slice is min(NB - 1, (int)((t - t_min) * (NB / (end - t_min)))), computed in
+// the pre-pass alone: the map is non-decreasing in t (equal times share a slice), so whole
+// slices are time cuts whatever the rounding, and nothing tests membership again.  A replica
+// with more arrivals than the merged capacity (RQ_ST_STREAM_OVERFLOW: decided before the
+// pre-pass, so out_len and the emitted prefix are the search loop's), with
+// a slice over FCAP (equal times among them), an inversion, a time outside [t_min, end] (NaN
+// too) or a stream past the 16-bit counts takes the search loop below for the whole replica
+// (block-uniform), which alone carries the one-ulp window, the NaN scale, the FCAP-at-a-time
+// emission and `while (t_lo <= end)`.  NB = 0: the search loop only (RQ_FLAT_SLICES=0).
+template <int FB, int FCAP, int FT8, int NB = 0>
 __global__ __launch_bounds__(FB) void rq_merge_flat(MergeArgs a)
 {
     constexpr int FW = FB / 64;            // waves
@@ -501,6 +534,12 @@ __global__ __launch_bounds__(FB) void rq_merge_flat(MergeArgs a)
     __shared__ uint32_t sbase[64];         // stream s's cursor as an index into the replica's streams
     __shared__ uint32_t wsum[2][FW], csum[FW];
     __shared__ double wmin[FW];
+    // the slice table's block-wide part (instances without it reference none of these)
+    __shared__ uint32_t tot[NB + 1];       // arrivals of all streams before slice b
+    __shared__ uint32_t slbad;             // the replica takes the search loop
+    // (cum_at masks a slice index with NB / 2 - 1: a power of two)
+    static_assert(NB == 0 || (LPS == 2 && NB >= 4 && (NB & (NB - 1)) == 0 && NB <= 64 && NB * 32 * 4 <= FCAP * 8),
+                  "slice table");
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int64_t rl = blockIdx.x;
@@ -539,71 +578,25 @@ __global__ __launch_bounds__(FB) void rq_merge_flat(MergeArgs a)
     uint16_t* out_j = a.out_j + rl * a.mrg_stride;
     int status = 0;
     int par = 1;   // wsum[par]: a retried window's sums are written while the last ones are read
+#ifdef RQ_PHASE_CLOCK
+    // diagnostic builds: thread 0's view of where a block's time goes (a.clk, scripts/dev/flat_clock.py)
+    unsigned long long ck[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tc0 = __builtin_amdgcn_s_memtime(), tc1 = 0;
+#define RQ_FLAT_TICK(q)                                                  \
+    do {                                                                 \
+        tc1 = __builtin_amdgcn_s_memtime();                              \
+        ck[q] += tc1 - tc0;                                              \
+        tc0 = tc1;                                                       \
+    } while (0)
+#else
+#define RQ_FLAT_TICK(q) do { } while (0)
+#endif
 
-    while (t_lo <= a.end) {
-        double tau = t_lo + span;
-        if (!(tau > t_lo)) tau = next_up(t_lo);
-        // ---- the stream's run [cur, lo): its arrivals before tau ----
-        // invariant: entries below lo are before tau, entries from hi on are not
-        int lo = cur, hi = L;
-        for (;;) {
-            const int n = hi - lo;
-            const bool act = n > 0;
-            if (!__ballot(act)) break;
-            // probes lo + n (k + 1) / (LPS + 1) < hi, non-decreasing in k
-            const uint32_t un = (uint32_t)(act ? n : 0);
-            bool below = false;
-            if (act) below = rep[off + (uint32_t)lo + un * (uint32_t)(k + 1) / (uint32_t)(LPS + 1)] < tau;
-            const uint64_t bal = __ballot(below);
-            const uint32_t c = (uint32_t)__popc((uint32_t)(bal >> g0l) & ((1u << LPS) - 1u));   // a prefix of the probes
-            if (act) {
-                if (c < (uint32_t)LPS) hi = lo + (int)(un * (c + 1u) / (uint32_t)(LPS + 1));
-                if (c > 0) lo = lo + (int)(un * c / (uint32_t)(LPS + 1)) + 1;
-            }
-        }
-        const int ns = lo - cur;
-        const uint32_t incl = wave_scan_add(k == 0 ? (uint32_t)ns : 0u);
-        if (lane == 63) wsum[par][w] = incl;
-        __syncthreads();
-        uint32_t wo = 0, nr_all = 0;
-#pragma unroll
-        for (int q = 0; q < FW; ++q) {
-            const uint32_t v = wsum[par][q];
-            wo += q < w ? v : 0u;
-            nr_all += v;
-        }
-        par ^= 1;
-        uint32_t nr = nr_all;
-        if (nr_all > (uint32_t)FCAP) {
-            if (tau != next_up(t_lo)) {   // too many for one window: halve the cut (nothing to undo)
-                span = (tau - t_lo) * 0.5;
-                continue;
-            }
-            // more than FCAP arrivals at t_lo itself: the first FCAP in (stream, position)
-            // order (any subset of equal times is a time prefix), and flag the replica
-            nr = FCAP;
-            status |= a.strict_ties ? RQ_ST_UNORDERED : RQ_ST_TIE;
-        }
-        if (outpos + (int64_t)nr > a.mrg_stride) {   // past the merged capacity (uniform)
-            status |= RQ_ST_STREAM_OVERFLOW;
-            break;
-        }
-        if (nr == 0) break;   // (the head at t_lo is before tau: only unordered input gets here)
-        {
-            // the group's lanes hold the same incl - ns: the items before their stream
-            const uint32_t e0 = wo + incl - (uint32_t)ns;
-            const int room = e0 < nr ? (int)(nr - e0) : 0;
-            if (k == 0) {
-                pre[s] = e0;
-                sbase[s] = off + (uint32_t)cur;
-            }
-            cur += ns < room ? ns : room;
-            head = RQ_INF;
-            if (k == 0 && cur < L) head = rep[off + (uint32_t)cur];   // used after the scatter
-        }
-        __syncthreads();
+    // One window: the nr arrivals in [w_lo, w_hi) -- stream s2's run starts at sbase[s2] and
+    // pre[s2] items come before it (both in LDS, a barrier behind them) -- through the item
+    // pass and (a)-(d).  `mid` runs between the scatter and its barrier.
+    auto window = [&](const double w_lo, const double w_hi, const uint32_t nr, auto&& mid) {
         // ---- the window's items into registers; (a) histogram ----
-        const double scale = (double)FM / (tau - t_lo);
+        const double scale = (double)FM / (w_hi - w_lo);
         double tv[PT];
         uint32_t kv[PT];
 #pragma unroll
@@ -618,10 +611,14 @@ __global__ __launch_bounds__(FB) void rq_merge_flat(MergeArgs a)
             tv[q] = rep[sbase[s2] + pos];
             kv[q] = (s2 << KB) | pos;
         }
+#ifdef RQ_PHASE_CLOCK
+        __builtin_amdgcn_s_waitcnt(0);   // the item loads' round trip on its own tick
+        RQ_FLAT_TICK(2);
+#endif
 #pragma unroll
         for (int q = 0; q < PT; ++q) {
             if ((uint32_t)(tid + q * FB) < nr) {
-                const uint32_t sb = (uint32_t)flat_sub<FM>(tv[q], t_lo, scale);
+                const uint32_t sb = (uint32_t)flat_sub<FM>(tv[q], w_lo, scale);
                 atomicAdd(&cnt[sb], 1u);
                 kv[q] |= sb << SB_SH;
             }
@@ -660,16 +657,14 @@ __global__ __launch_bounds__(FB) void rq_merge_flat(MergeArgs a)
                 sk[pos] = kv[q] & ((1u << SB_SH) - 1u);
             }
         }
-        {
-            const double m = wave_min_f64(head);
-            if (lane == 0) wmin[w] = m;
-        }
+        mid();
         __syncthreads();
+        RQ_FLAT_TICK(3);
         // ---- (d) rank inside the bucket, written out in play order ----
         for (int i = tid; i < (int)nr; i += FB) {
             const double x = st[i];
             const uint32_t kx = sk[i];
-            const int sb = flat_sub<FM>(x, t_lo, scale);
+            const int sb = flat_sub<FM>(x, w_lo, scale);
             const int g0 = sb > 0 ? (int)cnt[sb - 1] : 0, g1 = (int)cnt[sb];
             int r = 0;
             for (int q = g0; q < g1; ++q) {
@@ -683,6 +678,229 @@ __global__ __launch_bounds__(FB) void rq_merge_flat(MergeArgs a)
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < PT; ++q) cnt[tid + q * FB] = 0;   // the next histogram is two barriers away
+        RQ_FLAT_TICK(6);
+#ifdef RQ_PHASE_CLOCK
+        ck[4] += 1;
+#endif
+    };
+
+    bool by_table = false;
+    if constexpr (NB > 0) {
+        // a replica with nothing before the horizon's end has no window either way; one whose
+        // arrivals do not fit the merged capacity stops where the search loop's windows stop
+        // (out_len and the emitted prefix of an RQ_ST_STREAM_OVERFLOW replica are that loop's)
+        if (total > 0 && t_lo <= a.end && (int64_t)total <= a.mrg_stride) {
+            constexpr int HW = NB / 2;   // count words per stream: two 16-bit slice counts each
+            constexpr int CW = NB / 4;   // cum words per lane: the stream's lane k holds boundaries [k HW, k HW + HW)
+            // hist[g / 2][s]: the counts of slices g (even: low half) and g + 1 of stream s; it
+            // lies in st, which no window has written yet
+            uint32_t* hist = reinterpret_cast<uint32_t*>(st);
+            const double t_min = t_lo, wid = a.end - t_min;
+            for (int q = tid; q < HW * 64; q += FB) hist[q] = 0;
+            if (tid == 0) slbad = 0;
+            __syncthreads();
+            // ---- the pre-pass: lane k of a stream reads its 32-byte chunks k, k + 2, ... ----
+            const double inv = wid > 0.0 ? (double)NB / wid : 0.0;
+            // (past 65,535 arrivals a stream's 16-bit slice count could carry into its neighbour's
+            // half of the word, and the totals would no longer show the slice over FCAP)
+            bool bad = L > 65535;
+            const int nch = (L + 3) >> 2, lastc = L > 0 ? (L - 1) & ~3 : 0;   // loads stay inside the last chunk
+            const double4* src4 = reinterpret_cast<const double4*>(rep + off);   // capacities are whole lines
+            double carry = -RQ_INF;   // lane 0: the entry before its chunk (the neighbour's last)
+            constexpr int BT = RQ_FLAT_BT;   // chunks in flight per lane
+            for (int c0 = 0; c0 < nch; c0 += 2 * BT) {   // the two lanes of a stream run together
+                double4 v[BT];
+#pragma unroll
+                for (int b = 0; b < BT; ++b) {
+                    const int i4 = 4 * (c0 + 2 * b + k);
+                    v[b] = src4[(i4 < lastc ? i4 : lastc) >> 2];
+                }
+#pragma unroll
+                for (int b = 0; b < BT; ++b) {
+                    const int i4 = 4 * (c0 + 2 * b + k);
+                    const double nbw = flat_swap1_f64(v[b].w);
+                    const double pv = k ? nbw : carry;
+                    carry = nbw;
+                    const double e[5] = {pv, v[b].x, v[b].y, v[b].z, v[b].w};
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        if (i4 + q < L) {
+                            const double t = e[q + 1];
+                            bad |= !(t >= t_min && t <= a.end) || t < e[q];
+                            const double x0 = (t - t_min) * inv, x = x0 > 0.0 ? x0 : 0.0;
+                            int g = x < (double)(NB - 1) ? (int)x : NB - 1;
+                            atomicAdd(&hist[(g >> 1) * 64 + s], 1u << ((g & 1) * 16));
+                        }
+                    }
+                }
+            }
+            if (bad) slbad = 1;
+            __syncthreads();
+            // ---- cum: lane k's half of the stream's counts, summed from the stream's start ----
+            uint32_t cw[CW];
+            {
+                uint32_t run = 0;
+#pragma unroll
+                for (int r = 0; r < CW; ++r) {
+                    const uint32_t h = hist[(k * CW + r) * 64 + s];
+                    cw[r] = run | ((run + (h & 0xFFFFu)) << 16);
+                    run += (h & 0xFFFFu) + (h >> 16);
+                }
+                const uint32_t nbrun = flat_swap1(run);   // (both lanes active: a DPP read of an idle lane gives 0)
+                const uint32_t first = k ? nbrun : 0u;    // lane 1: what lane 0's half holds
+#pragma unroll
+                for (int r = 0; r < CW; ++r) cw[r] += first | (first << 16);
+            }
+            // ---- tot: thread b sums slice b over the streams (rotated: no two words of a step share a bank) ----
+            if (w == 0) {
+                uint32_t sl = 0;
+                if (tid < NB)
+#pragma unroll 16
+                    for (int q = 0; q < 64; ++q)
+                        sl += (hist[(tid >> 1) * 64 + ((q + (tid >> 1)) & 63)] >> ((tid & 1) * 16)) & 0xFFFFu;
+                if (sl > (uint32_t)FCAP) slbad = 1;
+                const uint32_t ti = wave_scan_add(sl);
+                if (tid < NB) tot[tid + 1] = ti;
+                if (tid == 0) tot[0] = 0;
+            }
+            __syncthreads();
+            RQ_FLAT_TICK(7);
+            // cum[s][b] in both lanes of stream s (b is block-uniform: the selects are scalar-controlled)
+            auto cum_at = [&](const int b) -> uint32_t {
+                const int idx = b & (HW - 1);
+                // a tree of selects on the index's bits (indexing cw would put it in scratch memory)
+                uint32_t y4[CW];
+#pragma unroll
+                for (int r = 0; r < CW; ++r) y4[r] = cw[r];
+#pragma unroll
+                for (int h = 1; h < CW; h <<= 1)
+#pragma unroll
+                    for (int r = 0; r < CW; r += 2 * h) y4[r] = ((idx >> 1) & h) ? y4[r + h] : y4[r];
+                uint32_t x = y4[0];
+                x = (idx & 1) ? x >> 16 : x & 0xFFFFu;
+                const uint32_t y = flat_swap1(x);
+                return b >= NB ? (uint32_t)L : ((b >= HW) == (k != 0) ? x : y);
+            };
+            auto tot_at = [&](const int b) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)tot[b]); };
+            if (!__builtin_amdgcn_readfirstlane((int)slbad)) {
+                by_table = true;
+                int b0 = 0;
+                while (b0 < NB) {
+                    // the longest run of slices from b0 that a window holds (every slice alone does)
+                    const uint32_t tb0 = tot_at(b0);
+                    int b1 = b0 + 1;
+                    while (b1 < NB && tot_at(b1 + 1) - tb0 <= (uint32_t)FCAP) ++b1;
+                    const uint32_t nr = tot_at(b1) - tb0;
+                    if (outpos + (int64_t)nr > a.mrg_stride) {   // past the merged capacity (uniform)
+                        status |= RQ_ST_STREAM_OVERFLOW;
+                        break;
+                    }
+                    if (nr == 0) {   // empty slices to the end
+                        b0 = b1;
+                        continue;
+                    }
+                    const uint32_t c0 = cum_at(b0), ns = cum_at(b1) - c0;
+                    const uint32_t incl = wave_scan_add(k == 0 ? ns : 0u);
+                    if (lane == 63) wsum[par][w] = incl;
+                    __syncthreads();
+                    uint32_t wo = 0;
+#pragma unroll
+                    for (int q = 0; q < FW; ++q) wo += q < w ? wsum[par][q] : 0u;
+                    par ^= 1;
+                    if (k == 0) {
+                        pre[s] = wo + incl - ns;
+                        sbase[s] = off + c0;
+                    }
+                    RQ_FLAT_TICK(0);
+                    __syncthreads();
+                    RQ_FLAT_TICK(1);
+                    // the sub-buckets' range only shapes the window's internal sort
+                    window(t_min + wid * ((double)b0 / (double)NB), b1 < NB ? t_min + wid * ((double)b1 / (double)NB) : a.end,
+                           nr, []() {});
+                    outpos += nr;
+                    b0 = b1;
+                }
+            }
+#ifdef RQ_PHASE_CLOCK
+            else
+                ck[5] += 1ull << 32;   // a replica on the search loop
+#endif
+        }
+    }
+
+    if (!by_table) {
+    while (t_lo <= a.end) {
+        double tau = t_lo + span;
+        if (!(tau > t_lo)) tau = next_up(t_lo);
+        // ---- the stream's run [cur, lo): its arrivals before tau ----
+        // invariant: entries below lo are before tau, entries from hi on are not
+        int lo = cur, hi = L;
+        for (;;) {
+            const int n = hi - lo;
+            const bool act = n > 0;
+            if (!__ballot(act)) break;
+            // probes lo + n (k + 1) / (LPS + 1) < hi, non-decreasing in k
+            const uint32_t un = (uint32_t)(act ? n : 0);
+            bool below = false;
+            if (act) below = rep[off + (uint32_t)lo + un * (uint32_t)(k + 1) / (uint32_t)(LPS + 1)] < tau;
+            const uint64_t bal = __ballot(below);
+            const uint32_t c = (uint32_t)__popc((uint32_t)(bal >> g0l) & ((1u << LPS) - 1u));   // a prefix of the probes
+            if (act) {
+                if (c < (uint32_t)LPS) hi = lo + (int)(un * (c + 1u) / (uint32_t)(LPS + 1));
+                if (c > 0) lo = lo + (int)(un * c / (uint32_t)(LPS + 1)) + 1;
+            }
+        }
+        const int ns = lo - cur;
+        const uint32_t incl = wave_scan_add(k == 0 ? (uint32_t)ns : 0u);
+        if (lane == 63) wsum[par][w] = incl;
+        __syncthreads();
+        uint32_t wo = 0, nr_all = 0;
+#pragma unroll
+        for (int q = 0; q < FW; ++q) {
+            const uint32_t v = wsum[par][q];
+            wo += q < w ? v : 0u;
+            nr_all += v;
+        }
+        par ^= 1;
+        uint32_t nr = nr_all;
+        if (nr_all > (uint32_t)FCAP) {
+            if (tau != next_up(t_lo)) {   // too many for one window: halve the cut (nothing to undo)
+                span = (tau - t_lo) * 0.5;
+#ifdef RQ_PHASE_CLOCK
+                ck[5] += 1;
+#endif
+                RQ_FLAT_TICK(0);
+                continue;
+            }
+            // more than FCAP arrivals at t_lo itself: the first FCAP in (stream, position)
+            // order (any subset of equal times is a time prefix), and flag the replica
+            nr = FCAP;
+            status |= a.strict_ties ? RQ_ST_UNORDERED : RQ_ST_TIE;
+        }
+        if (outpos + (int64_t)nr > a.mrg_stride) {   // past the merged capacity (uniform)
+            status |= RQ_ST_STREAM_OVERFLOW;
+            break;
+        }
+        if (nr == 0) break;   // (the head at t_lo is before tau: only unordered input gets here)
+        RQ_FLAT_TICK(0);
+        {
+            // the group's lanes hold the same incl - ns: the items before their stream
+            const uint32_t e0 = wo + incl - (uint32_t)ns;
+            const int room = e0 < nr ? (int)(nr - e0) : 0;
+            if (k == 0) {
+                pre[s] = e0;
+                sbase[s] = off + (uint32_t)cur;
+            }
+            cur += ns < room ? ns : room;
+            head = RQ_INF;
+            if (k == 0 && cur < L) head = rep[off + (uint32_t)cur];   // used after the scatter
+        }
+        __syncthreads();
+        RQ_FLAT_TICK(1);
+        window(t_lo, tau, nr, [&]() {
+            const double m = wave_min_f64(head);
+            if (lane == 0) wmin[w] = m;
+        });
         double t_next = wmin[0];
 #pragma unroll
         for (int q = 1; q < FW; ++q) t_next = wmin[q] < t_next ? wmin[q] : t_next;
@@ -693,6 +911,15 @@ __global__ __launch_bounds__(FB) void rq_merge_flat(MergeArgs a)
         span = wdt * (f < 4.0 ? f : 4.0);
         t_lo = t_next;   // the heads after the window (an equal-time window: t_lo again)
     }
+    }
+#ifdef RQ_PHASE_CLOCK
+    // phases: 0 run search (table: cum selects + scan), 1 pre / sbase and their barriers, 2 item
+    // loads, 3 histogram + scan + scatter, 6 rank + write-out, 7 the table's pre-pass; 4 windows,
+    // 5 retried windows + (replicas on the search loop << 32)
+    if (a.clk && tid == 0)
+        for (int q = 0; q < 8; ++q) atomicAdd(&a.clk[q], ck[q]);
+#endif
+#undef RQ_FLAT_TICK
     if (tid == 0) {
         a.out_len[rl] = (int)outpos;
         if (status) atomicOr(&a.status[a.chunk0 + rl], status);
@@ -782,28 +1009,41 @@ hipError_t rq_launch_merge(const MergeArgs& a, hipStream_t s)
     const char* ef = getenv("RQ_MERGE_FLAT");
     const int flat = ef ? atoi(ef) : 1;
     if (small_on && flat != 0 && a.n_str <= 64 && a.capsum < ((int64_t)1 << 31)) {
-#define RQ_FLAT_LAUNCH(FB, FCAP, FT8) \
-    hipLaunchKernelGGL((rq_merge_flat<FB, FCAP, FT8>), dim3((unsigned)a.n_chunk), dim3(FB), 0, s, a)
+        // RQ_FLAT_SLICES=0: the search loop for every replica (A/B and tests)
+        const char* es = getenv("RQ_FLAT_SLICES");
+        const int slices = es ? atoi(es) : 1;
+#define RQ_FLAT_LAUNCH(FB, FCAP, FT8, NB) \
+    hipLaunchKernelGGL((rq_merge_flat<FB, FCAP, FT8, NB>), dim3((unsigned)a.n_chunk), dim3(FB), 0, s, a)
 #ifdef RQ_FLAT_SHAPES
         // tuning builds (EXTRA=-DRQ_FLAT_SHAPES): RQ_MERGE_FLAT = waves * 100000 + window
         // capacity * 10 + eighths of it a window aims at (DESIGN 22 has the measurements)
         switch (flat) {
-        case 102566: RQ_FLAT_LAUNCH(64, 256, 6); return hipGetLastError();
-        case 105126: RQ_FLAT_LAUNCH(64, 512, 6); return hipGetLastError();
-        case 205126: RQ_FLAT_LAUNCH(128, 512, 6); return hipGetLastError();
-        case 210245: RQ_FLAT_LAUNCH(128, 1024, 5); return hipGetLastError();
-        case 210246: RQ_FLAT_LAUNCH(128, 1024, 6); return hipGetLastError();
-        case 215366: RQ_FLAT_LAUNCH(128, 1536, 6); return hipGetLastError();
-        case 220486: RQ_FLAT_LAUNCH(128, 2048, 6); return hipGetLastError();
-        case 410246: RQ_FLAT_LAUNCH(256, 1024, 6); return hipGetLastError();
-        case 410247: RQ_FLAT_LAUNCH(256, 1024, 7); return hipGetLastError();
-        case 420486: RQ_FLAT_LAUNCH(256, 2048, 6); return hipGetLastError();
-        case 430726: RQ_FLAT_LAUNCH(256, 3072, 6); return hipGetLastError();
-        case 820486: RQ_FLAT_LAUNCH(512, 2048, 6); return hipGetLastError();
+        case 102566: RQ_FLAT_LAUNCH(64, 256, 6, 0); return hipGetLastError();
+        case 105126: RQ_FLAT_LAUNCH(64, 512, 6, 0); return hipGetLastError();
+        case 205126: RQ_FLAT_LAUNCH(128, 512, 6, 0); return hipGetLastError();
+        case 210245: RQ_FLAT_LAUNCH(128, 1024, 5, 0); return hipGetLastError();
+        case 210246: RQ_FLAT_LAUNCH(128, 1024, 6, 0); return hipGetLastError();
+        case 215366: RQ_FLAT_LAUNCH(128, 1536, 6, 0); return hipGetLastError();
+        case 220486: RQ_FLAT_LAUNCH(128, 2048, 6, 0); return hipGetLastError();
+        case 410246: RQ_FLAT_LAUNCH(256, 1024, 6, 0); return hipGetLastError();
+        case 410247: RQ_FLAT_LAUNCH(256, 1024, 7, 0); return hipGetLastError();
+        case 420486: RQ_FLAT_LAUNCH(256, 2048, 6, 0); return hipGetLastError();
+        case 430726: RQ_FLAT_LAUNCH(256, 3072, 6, 0); return hipGetLastError();
+        case 820486: RQ_FLAT_LAUNCH(512, 2048, 6, 0); return hipGetLastError();
+        default: break;
+        }
+        // ... and RQ_FLAT_SLICES = the slice count of the launched shape's table
+        switch (slices) {
+        case 16: RQ_FLAT_LAUNCH(128, 1024, 7, 16); return hipGetLastError();
+        case 32: RQ_FLAT_LAUNCH(128, 1024, 7, 32); return hipGetLastError();
+        case 64: RQ_FLAT_LAUNCH(128, 1024, 7, 64); return hipGetLastError();
         default: break;
         }
 #endif
-        RQ_FLAT_LAUNCH(128, 1024, 7);
+        if (slices != 0)
+            RQ_FLAT_LAUNCH(128, 1024, 7, RQ_FLAT_NB);
+        else
+            RQ_FLAT_LAUNCH(128, 1024, 7, 0);
 #undef RQ_FLAT_LAUNCH
         return hipGetLastError();
     }
