@@ -48,7 +48,9 @@
  *                       int_r_2 / num_tweets_of over the whole horizon, exact on
  *                       equal times                          utils.py:38-56, :84-121, :170-176
  *                       for every replica of a batch of event logs at once
- *   rq_log_game         Opt broadcasters among SimOpts.other_sources  opt_model.py:761,
+ *   rq_log_metrics_of   the same with src_id = any source of the graph, on the df or on
+ *                       df[df.sink_id.isin(its followers)], several sources in one call
+ *   rq_log_game        Opt broadcasters among SimOpts.other_sources  opt_model.py:761,
  *                       each Opt.get_next_interval :502-544 in run_dynamic's loop :271-309
  *
  * Conventions
@@ -623,6 +625,58 @@ int rq_log_metrics(rq_graph_t g, const double* ev_t, const int32_t* ev_src,
                    int64_t* out_counts,   /* device [n_rep][4] */
                    int32_t* status,       /* device [n_rep] */
                    void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* rq_log_metrics for any source of the graph, several in one call: the reference's
+ * time_in_top_k(df, K, src_id=c), average_rank(df, src_id=c) and int_r_2 for src_id = c
+ * (utils.py:84-121 take any src_id), on the log's dataframe (scope RQ_LOG_OF_DF) or on
+ * df[df.sink_id.isin(followers of c)] (scope RQ_LOG_OF_OWN: the feeds an Opt tracks its
+ * rank on, opt_model.py:505).
+ *   For the tracked source c = src_ids[k] the outputs at [i][k] -- metrics [nK + 2],
+ * out_counts [4], status -- are rq_log_metrics' outputs for replica i with two changes:
+ *   1. "the controlled stream" is read as "stream c";
+ *   2. in scope RQ_LOG_OF_OWN the graph's edges are restricted to those whose sink is a
+ *      follower of c, i.e. a sink of one of c's edges.  An event with no edge into c's
+ *      followers then gives no row: it is not counted and makes no pivot row (inside a
+ *      t-group whose other events reach them it adds nothing).  The pivot columns are the
+ *      followers of c that get a row anywhere in the replica, and status is RQ_ST_EMPTY
+ *      (metrics NaN, counts 0) when no event reaches them -- always for a c without edges.
+ * Everything else is rq_log_metrics' word for word: t-groups; pandas' pivot mean on ties;
+ * the exact integer rowsum, or numpy's pairwise sum over the replica's own columns in
+ * ascending sink id; numpy's 8192-row chunked sums; out_counts = [c's events with a row,
+ * the other streams' with a row, pivot rows, S]; RQ_ST_TIE as informational; the clamping
+ * of counts[i][2]; stream indices outside the graph.  No replica's and no source's output
+ * depends on its neighbours, on the order of src_ids or on the launch; every output element
+ * is stored once.
+ *   So: scope RQ_LOG_OF_DF with src_ids = { ctrl_src_id } equals rq_log_metrics bit for
+ * bit; the values for c in scope DF equal rq_metrics_replay_batch(..., src_id = c, ...) on
+ * the rq_log_expand rows, and in scope OWN on those rows with the rows of other sinks
+ * removed.
+ *   src_ids: host [n_src], any order, each a stream of the graph (rq_graph_source_ids; the
+ * controlled one is allowed).  The tracked stream indices travel in the kernel's arguments:
+ * no staging, no allocation; the call only enqueues on hip_stream.  workspace: as
+ * rq_log_metrics', rq_log_metrics_of_workspace bytes (a block's pivot rows; it grows with
+ * ev_cap and with n_rep * n_src up to 4096 blocks -- a block plays its (replica, source)
+ * items one after the other).
+ *   RQ_EINVAL, before any HIP call: a null pointer, n_src outside 1..RQ_LOG_OF_MAX_SRC, an
+ * id that is no stream of the graph or is named twice, a scope other than the two, and
+ * rq_log_metrics' own cases.  RQ_EUNSUPPORTED exactly where rq_log_metrics returns it
+ * (duplicate edges, more than RQ_LOG_METRICS_MAX_SINKS sinks, ev_cap > 2^20); the workspace
+ * query answers the same.  A refused call launches nothing.
+ *   Added without an ABI version change (RQ_ABI_VERSION stays 6); a caller detects the
+ * functions by their symbols. */
+#define RQ_LOG_OF_DF  0   /* pivot columns: every sink the replica's log reaches (the df's) */
+#define RQ_LOG_OF_OWN 1   /* pivot columns: the tracked source's own followers only */
+#define RQ_LOG_OF_MAX_SRC 64
+int rq_log_metrics_of_workspace(rq_graph_t g, int32_t n_src, int64_t n_rep, int64_t ev_cap,
+                                int32_t nK, size_t* bytes);
+int rq_log_metrics_of(rq_graph_t g, const int64_t* src_ids /* host [n_src] */, int32_t n_src,
+                      int32_t scope, const double* ev_t, const int32_t* ev_src,
+                      const int64_t* counts, int64_t n_rep, int64_t ev_cap,
+                      const int32_t* Ks, int32_t nK,
+                      double* metrics,      /* device [n_rep][n_src][nK + 2] */
+                      int64_t* out_counts,  /* device [n_rep][n_src][4] */
+                      int32_t* status,      /* device [n_rep][n_src] */
+                      void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /* Competing RedQueen broadcasters (Opt among SimOpts.other_sources, opt_model.py:493-544,
  * :761): several Opts -- the PLAYERS -- post against each other and against an exogenous

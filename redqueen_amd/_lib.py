@@ -70,6 +70,8 @@ TIMELINE_MAX_SINKS = 12288   # RQ_TIMELINE_MAX_SINKS
 FOLLOWERS_TILED_MAX_SINKS = 40960   # RQ_FOLLOWERS_TILED_MAX_SINKS
 RANK_HIST_MAX_RANKS = 255    # RQ_RANK_HIST_MAX_RANKS
 LOG_METRICS_MAX_SINKS = 9800   # RQ_LOG_METRICS_MAX_SINKS
+LOG_OF_DF, LOG_OF_OWN = 0, 1   # RQ_LOG_OF_DF, RQ_LOG_OF_OWN: the scope of rq_log_metrics_of
+LOG_OF_MAX_SRC = 64            # RQ_LOG_OF_MAX_SRC
 
 _P = C.c_void_p
 _pd = C.POINTER(C.c_double)
@@ -126,6 +128,13 @@ class RQError(RuntimeError):
 
 
 _lib = None
+# entries added without an ABI version change that lib() does not insist on
+OPTIONAL = ("rq_log_metrics_of_workspace", "rq_log_metrics_of")
+
+
+def has(fn):
+    """Whether the loaded librq.so exports ``fn`` (an OPTIONAL entry)."""
+    return hasattr(lib(), fn)
 
 
 def lib():
@@ -191,6 +200,15 @@ def lib():
     L.rq_log_metrics.argtypes = [_P, _P, _P, _P, C.c_int64, C.c_int64, _pi32, C.c_int32, _P, _P, _P, _P,
                                  C.c_size_t, _P]
     L.rq_log_metrics.restype = C.c_int
+    # OPTIONAL symbols: an A/B build from before them (RQ_SO_PATH) still loads; calling one
+    # it lacks is an error (has())
+    if all(hasattr(L, fn) for fn in OPTIONAL):
+        L.rq_log_metrics_of_workspace.argtypes = [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                                  C.POINTER(C.c_size_t)]
+        L.rq_log_metrics_of_workspace.restype = C.c_int
+        L.rq_log_metrics_of.argtypes = [_P, _pi64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, C.c_int64,
+                                        _pi32, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]
+        L.rq_log_metrics_of.restype = C.c_int
     L.rq_timing.argtypes = [C.c_int]
     L.rq_timing_read.argtypes = [_pd, _pi64]
     for fn in ("rq_timing", "rq_timing_read", "rq_graph_build", "rq_graph_free", "rq_graph_info", "rq_graph_source_ids",
@@ -247,7 +265,8 @@ EXPORTED = ["rq_abi_version", "rq_strerror", "rq_graph_build", "rq_graph_free", 
             "rq_metrics_replay", "rq_metrics_replay_batch", "rq_oracle_workspace_size", "rq_oracle_dp", "rq_rank_table",
             "rq_u_int", "rq_log_rows", "rq_log_expand", "rq_log_timeline", "rq_log_followers",
             "rq_log_followers_tiled_workspace", "rq_log_followers_tiled",
-            "rq_log_rank_hist", "rq_log_metrics_workspace", "rq_log_metrics", "rq_log_game_workspace", "rq_log_game",
+            "rq_log_rank_hist", "rq_log_metrics_workspace", "rq_log_metrics",
+            "rq_log_metrics_of_workspace", "rq_log_metrics_of", "rq_log_game_workspace", "rq_log_game",
             "rq_timing", "rq_timing_read"]
 # rq_log_followers_max_sinks, rq_log_followers_tile_sinks and rq_log_game_table_in_lds return
 # int32_t, no status

@@ -290,6 +290,63 @@ def followers_frame(sink_ids, Ks, vals, rows, status):
     return pd.DataFrame(d)
 
 
+def run_sources(sim_opts, seeds=range(10), src_ids=None, scope="own", Ks=(1,), ctrl="opt", randomize=True,
+                chunk_replicas=None, **run_kw):
+    """The ensemble's metrics per source (BatchResult.source_metrics): returns
+    (``frame``, ``summary``).  ``frame`` is long-form, one row per (replica, src_id), with
+    ``replica`` (the seed's position), ``src_id``, the metrics (top_K..., avg_rank, r_2),
+    ``num_events`` (the source's events with a row), ``other_events`` and ``status``;
+    ``summary`` has one row per source with every metric's and count's mean and standard
+    error over the replicas whose status is not ST_EMPTY, plus ``n`` and ``n_empty`` (ties
+    are exact here, so ST_TIE replicas are averaged).  ``src_ids``: default the game's
+    players, else every source of the graph; ``scope`` "own" (the source's followers' feeds)
+    or "df".  Seeds, chunks and ``run_kw`` as in run_timeline: every chunk's values are
+    gathered on the host and reduced in seed order."""
+    met, cnt, sts = [], [], []
+    sm = None
+    for res in _seed_chunks(sim_opts, seeds, Ks, ctrl, randomize, chunk_replicas, run_kw, "run_sources"):
+        sm = res.source_metrics(src_ids, scope=scope, Ks=Ks)
+        met.append(sm.metrics.cpu().numpy())
+        cnt.append(sm.counts.cpu().numpy())
+        sts.append(sm.status.cpu().numpy())
+        del res
+    return sources_frame(sm.src_ids, sm.Ks, np.concatenate(met), np.concatenate(cnt), np.concatenate(sts))
+
+
+def sources_frame(src_ids, Ks, metrics, counts, status):
+    """run_sources' frames from per-replica values ([R, P, nK + 2], [R, P, 4], [R, P]):
+    the long-form frame, and per source the means and standard errors (sample standard
+    deviation / sqrt(n)) over the replicas that are not ST_EMPTY, summed in replica order."""
+    from ._lib import ST_EMPTY
+    metrics = np.asarray(metrics, dtype=np.float64)
+    counts, status = np.asarray(counts), np.asarray(status)
+    R, P = status.shape
+    names = ["top_" + str(k) for k in Ks] + ["avg_rank", "r_2"]
+    d = {"replica": np.repeat(np.arange(R, dtype=np.int64), P),
+         "src_id": np.tile(np.asarray(src_ids, dtype=np.int64), R)}
+    for i, nm in enumerate(names):
+        d[nm] = metrics[:, :, i].reshape(-1)
+    d["num_events"] = counts[:, :, 0].reshape(-1).astype(np.int64)
+    d["other_events"] = counts[:, :, 1].reshape(-1).astype(np.int64)
+    d["status"] = status.reshape(-1).astype(np.int64)
+    frame = pd.DataFrame(d)
+    v = np.concatenate([metrics, counts[:, :, :2].astype(np.float64)], axis=2)
+    cols = names + ["num_events", "other_events"]
+    s = {"src_id": np.asarray(src_ids, dtype=np.int64)}
+    mean, sem = np.full((P, len(cols)), np.nan), np.full((P, len(cols)), np.nan)
+    n = np.zeros(P, dtype=np.int64)
+    for p in range(P):
+        ok = (status[:, p] & ST_EMPTY) == 0
+        n[p] = int(ok.sum())
+        mean[p], sem[p] = _mean_sem(v[ok, p])
+    for i, nm in enumerate(cols):
+        s[nm] = mean[:, i]
+        s[nm + "_se"] = sem[:, i]
+    s["n"] = n
+    s["n_empty"] = R - n
+    return frame, pd.DataFrame(s)
+
+
 def run_rank_hist(sim_opts, seeds=range(10), ranks=64, bins=None, edges=None, ctrl="opt",
                   randomize=True, chunk_replicas=None, **run_kw):
     """The ensemble's rank distribution over time: one row per (time bin, rank cell) with

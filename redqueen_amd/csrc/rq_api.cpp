@@ -1276,6 +1276,55 @@ int rq_log_metrics(rq_graph_t g, const double* ev_t, const int32_t* ev_src, cons
     return rq_launch_log_metrics(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
 }
 
+// the blocks of an rq_log_metrics_of launch: one per (replica, source) up to the slot count
+static int64_t log_of_slots(int64_t n_rep, int32_t n_src)
+{
+    const int slots = std::min(rqh::read_knobs().lm_of_slots, RQ_LM_SLOTS);
+    return rqh::log_of_blocks(n_rep, n_src, slots);
+}
+
+int rq_log_metrics_of_workspace(rq_graph_t g, int32_t n_src, int64_t n_rep, int64_t ev_cap, int32_t nK,
+                                size_t* bytes)
+{
+    if (!bytes || n_src < 1 || n_src > RQ_LOG_OF_MAX_SRC) return RQ_EINVAL;
+    const int rc = log_metrics_check(g, n_rep, ev_cap, nK);
+    if (rc != RQ_OK) return rc;
+    *bytes = (size_t)log_of_slots(n_rep, n_src) * rq_log_metrics_slot_bytes(ev_cap, nK);
+    return RQ_OK;
+}
+
+int rq_log_metrics_of(rq_graph_t g, const int64_t* src_ids, int32_t n_src, int32_t scope, const double* ev_t,
+                      const int32_t* ev_src, const int64_t* counts, int64_t n_rep, int64_t ev_cap,
+                      const int32_t* Ks, int32_t nK, double* metrics, int64_t* out_counts, int32_t* status,
+                      void* workspace, size_t workspace_bytes, void* hip_stream)
+{
+    if (!g || !src_ids || !ev_t || !ev_src || !counts || !metrics || !out_counts || !status || !workspace)
+        return RQ_EINVAL;
+    if (scope != RQ_LOG_OF_DF && scope != RQ_LOG_OF_OWN) return RQ_EINVAL;
+    LogMetricsOfArgs b{};
+    LogMetricsArgs& a = b.m;
+    if (rqh::log_of_streams(*g, src_ids, n_src, b.trk) != RQ_OK) return RQ_EINVAL;
+    if (!copy_ks(Ks, nK, a.Ks)) return RQ_EINVAL;
+    const int rc = log_metrics_check(g, n_rep, ev_cap, nK);
+    if (rc != RQ_OK) return rc;
+    a.n_slots = (int)log_of_slots(n_rep, n_src);
+    a.slot_bytes = rq_log_metrics_slot_bytes(ev_cap, nK);
+    if (workspace_bytes < (size_t)a.n_slots * a.slot_bytes || (reinterpret_cast<uintptr_t>(workspace) & 7))
+        return RQ_EINVAL;
+    a.log = log_view(g, ev_t, ev_src, counts, n_rep, ev_cap);
+    a.nK = nK;
+    a.state_bytes = rq_log_metrics_state_bytes(g->n_sinks, g->n_str);
+    a.rows = static_cast<char*>(workspace);
+    a.metrics = metrics;
+    a.out_counts = out_counts;
+    a.status = status;
+    b.n_src = n_src;
+    b.scope = scope;
+    hipStream_t st = (hipStream_t)hip_stream;
+    TimedLaunch tl(K_REPLAY, st);
+    return rq_launch_log_metrics_of(b, st) == hipSuccess ? RQ_OK : RQ_EHIP;
+}
+
 int rq_log_game_workspace(rq_graph_t g, int32_t n_players, size_t* bytes)
 {
     if (!g || !bytes || n_players < 1) return RQ_EINVAL;

@@ -172,6 +172,12 @@ struct Knobs {
     bool rp_small = true;
     // RQ_CLK_REPLAY: RQ_PHASE_CLOCK builds only, rq_rp_fast's phase clocks (scripts/dev/replay_clock.py)
     bool clk_replay = false;
+
+    // -- rq_log_metrics_of --
+    // RQ_LM_OF_SLOTS: blocks (workspace slots) of a launch, clamped to 1..4096 (the default);
+    // tests only (test_gpu_log_sources: tiny batches past the slot count, where a block plays
+    // runs of sources)
+    int lm_of_slots = 4096;
 };
 Knobs read_knobs();
 
@@ -341,5 +347,16 @@ inline size_t game_ws_bytes(int n_str, int P)
 }
 // RQ_OK, or the rq_status rq_log_game returns for these players on this graph
 int game_tables(const GraphTopo& g, const rq_game_player* players, int n_players, GameTables* out);
+
+// ---- the tracked sources of rq_log_metrics_of (include/rq.h) ----
+// trk[k] = the stream index of src_ids[k]; RQ_EINVAL for n_src outside 1..RQ_LOG_OF_MAX_SRC,
+// an id that is no stream of the graph or an id named twice (trk is then unspecified)
+int log_of_streams(const GraphTopo& g, const int64_t* src_ids, int n_src, int* trk);
+// blocks (= workspace slots) of a launch over n_rep * n_src work items
+inline int64_t log_of_blocks(int64_t n_rep, int n_src, int slots)
+{
+    const int64_t items = n_rep * (int64_t)n_src;
+    return items < slots ? items : slots;
+}
 
 }  // namespace rqh

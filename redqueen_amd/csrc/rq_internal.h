@@ -477,6 +477,23 @@ struct LogMetricsArgs {
 };
 hipError_t rq_launch_log_metrics(const LogMetricsArgs& a, hipStream_t s);
 
+// rq_log_metrics_of: the same play for n_src tracked streams.  The work items (replica,
+// tracked source) are dealt to m.n_slots blocks in contiguous ranges, so a block plays, per
+// replica it meets, a run of consecutive tracked sources in its slot; while n_rep * n_src <=
+// the slot count every run is one source long.  Outputs are indexed [replica][source].
+struct LogMetricsOfArgs {
+    LogMetricsArgs m;         // m.log.ctrl_idx is not read; m.n_slots = min(n_rep * n_src, slots)
+    int trk[RQ_LOG_OF_MAX_SRC];   // stream index of src_ids[k]
+    int n_src;
+    int scope;                // RQ_LOG_OF_DF / RQ_LOG_OF_OWN
+    double taper;             // set by the launch: 1, or RQ_LM_OF_TAPER when the blocks outnumber the resident ones
+};
+// shares of the work items fall from this many times the mean to 2 minus it (of_first_item)
+#ifndef RQ_LM_OF_TAPER
+#define RQ_LM_OF_TAPER 1.95
+#endif
+hipError_t rq_launch_log_metrics_of(const LogMetricsOfArgs& a, hipStream_t s);
+
 // ---- competing RedQueen broadcasters against an exogenous log (rq_game.hip) ----
 struct GameArgs {
     const double* ev_t;       // [n_rep][ev_cap] the exogenous logs

@@ -25,6 +25,15 @@
 //      in the merged fused sweep's epilogue (rq_sweep_fw.hip).
 // Every output element is stored once by lane 0 of its replica's wave.
 //
+// rq_log_metrics_of (rq_log_metrics_of_k) plays the same steps for any tracked streams:
+// steps 2 and 3 are one body, lm_play, instantiated for both kernels.  Its work items are
+// (replica, tracked source); a block plays a contiguous range of them in its slot.  "Own"
+// is the tracked stream (a LogView of the item with ctrl_idx = it).  Scope DF: step 1 does
+// not depend on the source, so xbits / xpre / S are kept while the replica stays the same.
+// Scope OWN: xbits is ANDed with the tracked stream's follower bits, built from its CSR row
+// where the cells will be, and step 2 (MASKED) plays a sink only if its bit is set; an
+// event none of whose sinks is set opens no t-group and is not counted.
+//
 // LDS (rq_log_metrics_lds_bytes): [scratch of wave_npsum<1> / scan_rows][Cell x n_sinks,
 // during step 1 the stream bits][xbits][xpre].  A Cell is 16 bytes -- rank i32, tag i32,
 // and sum << 24 | count in 64 bits (ev_cap <= 2^20: count <= 2^20, sum < 2^40) -- one
@@ -55,228 +64,371 @@ static_assert(sizeof(Cell) == RQ_LM_CELL_BYTES, "rq_log_metrics_lds_bytes");
 // rows per lane and trip of the scan (TU of wave_npsum_rows), as the fused sweep's fws_tu
 constexpr int lm_tu(int nk) { return nk == 1 ? 4 : 2; }
 
+// a block's wave: its LDS and its slot of the workspace
+struct LmWave {
+    double* scratch;
+    Cell* cell;
+    uint32_t* sbits;   // step 1 only, in the cells' place: the stream bits, then (scope OWN) the follower bits
+    uint32_t* xbits;
+    uint16_t* xpre;
+    double *Rt, *Rs;
+    uint32_t *Rv, *Rc;
+};
+
+__device__ __forceinline__ LmWave lm_wave(const LogMetricsArgs& a, char* lds)
+{
+    LmWave w;
+    const int W = (a.log.n_sinks + 31) >> 5;
+    w.scratch = reinterpret_cast<double*>(lds);
+    w.cell = reinterpret_cast<Cell*>(lds + RQ_LM_SCRATCH_BYTES);
+    w.sbits = reinterpret_cast<uint32_t*>(w.cell);
+    w.xbits = reinterpret_cast<uint32_t*>(lds + RQ_LM_SCRATCH_BYTES + a.state_bytes);
+    w.xpre = reinterpret_cast<uint16_t*>(w.xbits + W);
+    char* slot = a.rows + (size_t)blockIdx.x * a.slot_bytes;
+    w.Rt = reinterpret_cast<double*>(slot);
+    w.Rs = w.Rt + a.log.ev_cap;
+    w.Rv = reinterpret_cast<uint32_t*>(w.Rs + a.log.ev_cap);
+    w.Rc = w.Rv + a.log.ev_cap;
+    return w;
+}
+
+// step 1, the marks: xbits = the sinks replica r's log reaches
+__device__ __forceinline__ void lm_reached(const LogView& v, int64_t r, const LmWave& w)
+{
+    const int lane = lane_id();
+    const int NSTR = v.n_str;
+    const int W = (v.n_sinks + 31) >> 5, WS = (NSTR + 31) >> 5;
+    uint32_t* sbits = w.sbits;
+    uint32_t* xbits = w.xbits;
+    int64_t n = v.counts[r * 4 + 2];
+    n = n < 0 ? 0 : (n > v.ev_cap ? v.ev_cap : n);
+    const int32_t* J = v.ev_src + r * v.ev_cap;
+    for (int q = lane; q < WS; q += 64) sbits[q] = 0u;
+    for (int q = lane; q < W; q += 64) xbits[q] = 0u;
+    wave_lds_sync();
+    for (int64_t k0 = 0; k0 < n; k0 += 64) {
+        const int64_t k = k0 + lane;
+        if (k < n) {
+            const int j = J[k];
+            if ((unsigned)j < (unsigned)NSTR) atomicOr(&sbits[j >> 5], 1u << (j & 31));
+        }
+    }
+    wave_lds_sync();
+    for (int w0 = 0; w0 < WS; w0 += 64) {
+        const uint32_t m = w0 + lane < WS ? sbits[w0 + lane] : 0u;
+        uint64_t nz = __ballot(m != 0u);
+        while (nz) {
+            const int l = __ffsll((unsigned long long)nz) - 1;
+            nz &= nz - 1;
+            uint32_t mw = (uint32_t)bcast_i((int)m, l);
+            while (mw) {
+                const int j = (w0 + l) * 32 + (__ffs(mw) - 1);
+                mw &= mw - 1;
+                const int p0 = v.csr_ptr[j], p1 = v.csr_ptr[j + 1];
+                for (int e = p0 + lane; e < p1; e += 64) {
+                    const int x = v.csr_col[e];
+                    atomicOr(&xbits[x >> 5], 1u << (x & 31));
+                }
+            }
+        }
+    }
+    wave_lds_sync();
+}
+
+// scope OWN: xbits &= the followers of stream c, whose bits are built from its CSR row where
+// the stream bits were (every lane has read its words of them)
+__device__ __forceinline__ void lm_own_columns(const LogView& v, int c, const LmWave& w)
+{
+    const int lane = lane_id();
+    const int W = (v.n_sinks + 31) >> 5;
+    uint32_t* fbits = w.sbits;
+    for (int q = lane; q < W; q += 64) fbits[q] = 0u;
+    wave_lds_sync();
+    const int p0 = v.csr_ptr[c], p1 = v.csr_ptr[c + 1];
+    for (int e = p0 + lane; e < p1; e += 64) {
+        const int x = v.csr_col[e];
+        atomicOr(&fbits[x >> 5], 1u << (x & 31));
+    }
+    wave_lds_sync();
+    for (int q = lane; q < W; q += 64) w.xbits[q] &= fbits[q];
+    wave_lds_sync();
+}
+
+// step 1, the index: xpre of xbits; returns S
+__device__ __forceinline__ int lm_index(const LogView& v, const LmWave& w)
+{
+    const int lane = lane_id();
+    const int W = (v.n_sinks + 31) >> 5;
+    int S = 0;
+    for (int w0 = 0; w0 < W; w0 += 64) {
+        const int q = w0 + lane;
+        const uint32_t c = q < W ? (uint32_t)__popc(w.xbits[q]) : 0u;
+        const uint32_t inc = wave_scan_add(c);
+        if (q < W) w.xpre[q] = (uint16_t)(S + (int)(inc - c));
+        S += __builtin_amdgcn_readlane((int)inc, 63);
+    }
+    return S;
+}
+
+// S cells without a row (what step 1 kept in their place is dead: every lane read its words)
+__device__ __forceinline__ void lm_cells(int S, const LmWave& w)
+{
+    for (int c = lane_id(); c < S; c += 64) {
+        Cell z;
+        z.rank = -1;
+        z.tag = -1;
+        z.cs = 0;
+        w.cell[c] = z;
+    }
+    wave_lds_sync();
+}
+
+// Steps 2 and 3 of one replica for one tracked stream, log.ctrl_idx: the pivot rows of
+// replica r over the S columns of xbits / xpre, then counts, status and the integrals to
+// output element o.  MASKED (rq_log_metrics_of): a sink outside xbits gets no row, and an
+// event none of whose sinks is a column is no event -- it opens no t-group and is not counted
+// (xbits of rq_log_metrics holds every sink of every event, so there nothing is masked).
+template <int NK, bool MASKED>
+__device__ __forceinline__ void lm_play(const LogMetricsArgs& a, const LogView& log, int64_t r, int64_t o, int S,
+                                        const LmWave& w, const int64_t (&km1)[NK])
+{
+    constexpr int NV = NK + 2;
+    const int lane = lane_id();
+    double* scratch = w.scratch;
+    Cell* cell = w.cell;
+    const uint32_t* xbits = w.xbits;
+    const uint16_t* xpre = w.xpre;
+    double *Rt = w.Rt, *Rs = w.Rs;
+    uint32_t *Rv = w.Rv, *Rc = w.Rc;
+
+    // ---- 2. the pivot rows ----
+    int64_t sumI = 0;            // the sum of the integral cells
+    int nvalid = 0, nfrac = 0;   // columns with a cell; with a fractional one
+    int cK[NK];
+#pragma unroll
+    for (int q = 0; q < NK; ++q) cK[q] = 0;
+    int gid = 0;
+    bool have = false, tie = false;
+    double pend_t = 0.0;         // the open t-group's time
+    int64_t n_own = 0, n_oth = 0, nrow = 0;
+    double r_t = 0.0, r_s = 0.0;   // lane (row & 63) stages a row
+    int r_v = 0, r_c[NK];
+#pragma unroll
+    for (int q = 0; q < NK; ++q) r_c[q] = 0;
+
+    auto store_row = [&](int64_t rr) {
+        Rt[rr] = r_t;
+        Rs[rr] = r_s;
+        Rv[rr] = (uint32_t)r_v;
+#pragma unroll
+        for (int q = 0; q < NK; ++q) Rc[rr * NK + q] = (uint32_t)r_c[q];
+    };
+    auto emit = [&]() {   // the open group's pivot row
+        double rowsum;
+        if (nfrac == 0) {
+            rowsum = (double)sumI;
+        } else {
+            double o1[1];
+            wave_npsum<1>((int64_t)S,
+                          [&](int64_t k, double* v) {
+                              const Cell c = cell[k];
+                              v[0] = c.tag >= 0 ? (double)(int64_t)(c.cs >> 24) / (double)(int)(c.cs & 0xFFFFFFu)
+                                                : 0.0;
+                          },
+                          scratch, o1);
+            rowsum = o1[0];
+        }
+        const int sl = (int)(nrow & 63);
+        if (lane == sl) {
+            r_t = pend_t;
+            r_s = rowsum;
+            r_v = nvalid;
+#pragma unroll
+            for (int q = 0; q < NK; ++q) r_c[q] = cK[q];
+        }
+        if (sl == 63) store_row(nrow - 63 + lane);
+        ++nrow;
+    };
+    auto open = [&](double t, bool own) {   // an event with a row joins the open t-group or closes it
+        if (have && t != pend_t) {
+            emit();
+            ++gid;
+        }
+        have = true;
+        pend_t = t;
+        if (own) ++n_own;
+        else ++n_oth;
+    };
+
+    log_walk(log, r, [&](double t, bool own, int p0, int p1, int xfirst) {
+        bool opened = !MASKED;
+        if (!MASKED) open(t, own);
+        for (int e = p0; e < p1; e += 64) {
+            bool act = e + lane < p1;
+            const int x = row_sink(log, e, p0, act, xfirst);
+            bool ov = false, same = false;
+            int64_t sm = 0, ns = 0;
+            int k = 0, nk = 1;
+            // the sink's word of the column bits and its prefix: both reads leave together,
+            // before the mask is known, so masking adds no LDS round trip to an event
+            uint32_t wb = 0u;
+            int xp = 0;
+            if (act) {
+                wb = xbits[x >> 5];
+                xp = (int)xpre[x >> 5];
+            }
+            if (MASKED) {
+                act = act && ((wb >> (x & 31)) & 1u);
+                if (!__ballot(act)) continue;
+                if (!opened) open(t, own);
+                opened = true;
+            }
+            if (act) {
+                const int c = xp + __popc(wb & ((1u << (x & 31)) - 1u));
+                Cell s = cell[c];
+                ov = s.tag >= 0;
+                same = s.tag == gid;
+                k = (int)(s.cs & 0xFFFFFFu);
+                sm = (int64_t)(s.cs >> 24);
+                const int rn = next_rank(own, s.rank);
+                nk = same ? k + 1 : 1;
+                ns = same ? sm + rn : (int64_t)rn;
+                s.rank = rn;
+                s.tag = gid;
+                s.cs = ((uint64_t)ns << 24) | (uint32_t)nk;
+                cell[c] = s;
+            }
+            if (__ballot(same)) tie = true;
+            nvalid += popc(__ballot(act && !ov));
+            // the old cell sm / k and the new one ns / nk
+            const uint64_t means = __ballot(act && (nk > 1 || k > 1));
+            if (!means) {   // both are the integers sm and ns
+#pragma unroll
+                for (int q = 0; q < NK; ++q) {
+                    const bool a1 = act && ns <= km1[q], a0 = ov && sm <= km1[q];
+                    cK[q] += popc(__ballot(a1 && !a0)) - popc(__ballot(a0 && !a1));
+                }
+                // an own row: every new cell is 0; another's: old + 1, and 1 on a new column
+                if (own) sumI -= wave_sum_i64(ov ? sm : 0);
+                else sumI += popc(__ballot(act));
+            } else {
+                // a quotient of integers < 2^53 is exact when it is an integer, so
+                // trunc(q) * den == num holds for an integral cell and for no other
+                const int kk = k > 0 ? k : 1;
+                const int64_t oq = (int64_t)((double)sm / (double)kk);
+                const int64_t nq = (int64_t)((double)ns / (double)nk);
+                const bool oint = ov && oq * kk == sm;
+                const bool ofr = ov && !oint;
+                const bool nint = nq * nk == ns;
+                nfrac += popc(__ballot(act && !nint && !ofr)) - popc(__ballot(act && nint && ofr));
+#pragma unroll
+                for (int q = 0; q < NK; ++q) {
+                    const bool a1 = act && ns <= km1[q] * nk, a0 = ov && sm <= km1[q] * kk;
+                    cK[q] += popc(__ballot(a1 && !a0)) - popc(__ballot(a0 && !a1));
+                }
+                sumI += wave_sum_i64(act && nint ? nq : 0) - wave_sum_i64(oint ? oq : 0);
+            }
+        }
+        wave_lds_sync();
+    });
+    if (have) emit();
+    {   // the staged rows of the last, partial store
+        const int rem = (int)(nrow & 63);
+        if (lane < rem) store_row(nrow - rem + lane);
+    }
+
+    // ---- 3. counts, status and the integrals ----
+    if (lane == 0) {
+        int64_t* oc = a.out_counts + o * 4;
+        oc[0] = n_own;
+        oc[1] = n_oth;
+        oc[2] = nrow;
+        oc[3] = S;
+        a.status[o] = log_status(have, tie);
+    }
+    double* M = a.metrics + o * NV;
+    if (!have) {
+        if (lane < NV) M[lane] = __builtin_nan("");
+    } else {
+        // every row was stored by this wave: drain its stores, then order them before
+        // its loads at workgroup scope (same wave, same CU)
+        __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        double res[NV];
+        scan_rows<NK, lm_tu(NK), RQ_LM_NL>(nrow, (double)S, log.end, Rt, Rs, Rv, Rc, scratch, res);
+        if (lane == 0) {
+#pragma unroll
+            for (int q = 0; q < NV; ++q) M[q] = res[q];
+        }
+    }
+    wave_lds_sync();   // the scan's scratch and the cells before the next marks
+}
+
 template <int NK>
 __global__ __launch_bounds__(64) void rq_log_metrics_k(LogMetricsArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char lds_lm[];
-    constexpr int NV = NK + 2;
-    const int lane = lane_id();
-    const int NS = a.log.n_sinks, NSTR = a.log.n_str;
-    const int W = (NS + 31) >> 5, WS = (NSTR + 31) >> 5;
-    double* scratch = reinterpret_cast<double*>(lds_lm);
-    Cell* cell = reinterpret_cast<Cell*>(lds_lm + RQ_LM_SCRATCH_BYTES);
-    uint32_t* sbits = reinterpret_cast<uint32_t*>(cell);   // step 1 only
-    uint32_t* xbits = reinterpret_cast<uint32_t*>(lds_lm + RQ_LM_SCRATCH_BYTES + a.state_bytes);
-    uint16_t* xpre = reinterpret_cast<uint16_t*>(xbits + W);
-
-    // this block's rows
-    char* slot = a.rows + (size_t)blockIdx.x * a.slot_bytes;
-    double* Rt = reinterpret_cast<double*>(slot);
-    double* Rs = Rt + a.log.ev_cap;
-    uint32_t* Rv = reinterpret_cast<uint32_t*>(Rs + a.log.ev_cap);
-    uint32_t* Rc = Rv + a.log.ev_cap;
-
+    const LmWave w = lm_wave(a, lds_lm);
     int64_t km1[NK];
 #pragma unroll
     for (int q = 0; q < NK; ++q) km1[q] = (int64_t)a.Ks[q] - 1;
 
     for (int64_t r = blockIdx.x; r < a.log.n_rep; r += gridDim.x) {
-        // ---- 1. the replica's pivot columns ----
-        int64_t n = a.log.counts[r * 4 + 2];
-        n = n < 0 ? 0 : (n > a.log.ev_cap ? a.log.ev_cap : n);
-        const int32_t* J = a.log.ev_src + r * a.log.ev_cap;
-        for (int w = lane; w < WS; w += 64) sbits[w] = 0u;
-        for (int w = lane; w < W; w += 64) xbits[w] = 0u;
-        wave_lds_sync();
-        for (int64_t k0 = 0; k0 < n; k0 += 64) {
-            const int64_t k = k0 + lane;
-            if (k < n) {
-                const int j = J[k];
-                if ((unsigned)j < (unsigned)NSTR) atomicOr(&sbits[j >> 5], 1u << (j & 31));
-            }
-        }
-        wave_lds_sync();
-        for (int w0 = 0; w0 < WS; w0 += 64) {
-            const uint32_t m = w0 + lane < WS ? sbits[w0 + lane] : 0u;
-            uint64_t nz = __ballot(m != 0u);
-            while (nz) {
-                const int l = __ffsll((unsigned long long)nz) - 1;
-                nz &= nz - 1;
-                uint32_t mw = (uint32_t)bcast_i((int)m, l);
-                while (mw) {
-                    const int j = (w0 + l) * 32 + (__ffs(mw) - 1);
-                    mw &= mw - 1;
-                    const int p0 = a.log.csr_ptr[j], p1 = a.log.csr_ptr[j + 1];
-                    for (int e = p0 + lane; e < p1; e += 64) {
-                        const int x = a.log.csr_col[e];
-                        atomicOr(&xbits[x >> 5], 1u << (x & 31));
-                    }
-                }
-            }
-        }
-        wave_lds_sync();
-        int S = 0;
-        for (int w0 = 0; w0 < W; w0 += 64) {
-            const int w = w0 + lane;
-            const uint32_t c = w < W ? (uint32_t)__popc(xbits[w]) : 0u;
-            const uint32_t inc = wave_scan_add(c);
-            if (w < W) xpre[w] = (uint16_t)(S + (int)(inc - c));
-            S += __builtin_amdgcn_readlane((int)inc, 63);
-        }
-        for (int c = lane; c < S; c += 64) {   // the stream bits are dead: every lane read its words
-            Cell z;
-            z.rank = -1;
-            z.tag = -1;
-            z.cs = 0;
-            cell[c] = z;
-        }
-        wave_lds_sync();
+        lm_reached(a.log, r, w);
+        const int S = lm_index(a.log, w);
+        lm_cells(S, w);
+        lm_play<NK, false>(a, a.log, r, r, S, w, km1);
+    }
+}
 
-        // ---- 2. the pivot rows ----
-        int64_t sumI = 0;            // the sum of the integral cells
-        int nvalid = 0, nfrac = 0;   // columns with a cell; with a fractional one
-        int cK[NK];
-#pragma unroll
-        for (int q = 0; q < NK; ++q) cK[q] = 0;
-        int gid = 0;
-        bool have = false, tie = false;
-        double pend_t = 0.0;         // the open t-group's time
-        int64_t n_own = 0, n_oth = 0, nrow = 0;
-        double r_t = 0.0, r_s = 0.0;   // lane (row & 63) stages a row
-        int r_v = 0, r_c[NK];
-#pragma unroll
-        for (int q = 0; q < NK; ++q) r_c[q] = 0;
+// The first work item of block b of B.  taper 1: equal shares.  taper a in (1, 2], for
+// launches of more blocks than the device holds at once: shares falling linearly from a to
+// 2 - a times the mean.  The device starts blocks in index order as earlier ones end, so the
+// long ones go first and the short ones fill the tail, where equal shares leave most of the
+// device idle in the last round (C3, 17 players, 943 -> 792 ms).
+__device__ __forceinline__ int64_t of_first_item(int64_t n, unsigned b, unsigned B, double taper)
+{
+    if (taper > 1.0 && n >= 4 * (int64_t)B) {
+        const double u = (double)b / (double)B;
+        return b >= B ? n : (int64_t)((double)n * (u * (taper - (taper - 1.0) * u)));
+    }
+    return n * b / B;
+}
 
-        auto store_row = [&](int64_t rr) {
-            Rt[rr] = r_t;
-            Rs[rr] = r_s;
-            Rv[rr] = (uint32_t)r_v;
+// rq_log_metrics_of: block b plays the work items [n b / B, n (b + 1) / B) of the n = n_rep *
+// n_src items (replica, tracked source), item = replica * n_src + position in src_ids -- for
+// each replica it meets a run of consecutive tracked sources, played one after the other in
+// the block's slot.  Scope DF: the columns are the replica's, found once per run.  Scope OWN:
+// they are masked with the tracked source's followers, found again per source.
+template <int NK>
+__global__ __launch_bounds__(64) void rq_log_metrics_of_k(LogMetricsOfArgs b)
+{
+    extern __shared__ __attribute__((aligned(16))) char lds_lm[];
+    const LogMetricsArgs& a = b.m;
+    const LmWave w = lm_wave(a, lds_lm);
+    int64_t km1[NK];
 #pragma unroll
-            for (int q = 0; q < NK; ++q) Rc[rr * NK + q] = (uint32_t)r_c[q];
-        };
-        auto emit = [&]() {   // the open group's pivot row
-            double rowsum;
-            if (nfrac == 0) {
-                rowsum = (double)sumI;
-            } else {
-                double o[1];
-                wave_npsum<1>((int64_t)S,
-                              [&](int64_t k, double* v) {
-                                  const Cell c = cell[k];
-                                  v[0] = c.tag >= 0 ? (double)(int64_t)(c.cs >> 24) / (double)(int)(c.cs & 0xFFFFFFu)
-                                                    : 0.0;
-                              },
-                              scratch, o);
-                rowsum = o[0];
-            }
-            const int sl = (int)(nrow & 63);
-            if (lane == sl) {
-                r_t = pend_t;
-                r_s = rowsum;
-                r_v = nvalid;
-#pragma unroll
-                for (int q = 0; q < NK; ++q) r_c[q] = cK[q];
-            }
-            if (sl == 63) store_row(nrow - 63 + lane);
-            ++nrow;
-        };
+    for (int q = 0; q < NK; ++q) km1[q] = (int64_t)a.Ks[q] - 1;
 
-        log_walk(a.log, r, [&](double t, bool own, int p0, int p1, int xfirst) {
-            if (have && t != pend_t) {
-                emit();
-                ++gid;
-            }
-            have = true;
-            pend_t = t;
-            if (own) ++n_own;
-            else ++n_oth;
-            for (int e = p0; e < p1; e += 64) {
-                const bool act = e + lane < p1;
-                const int x = row_sink(a.log, e, p0, act, xfirst);
-                bool ov = false, same = false;
-                int64_t sm = 0, ns = 0;
-                int k = 0, nk = 1;
-                if (act) {
-                    const uint32_t wb = xbits[x >> 5];
-                    const int c = (int)xpre[x >> 5] + __popc(wb & ((1u << (x & 31)) - 1u));
-                    Cell s = cell[c];
-                    ov = s.tag >= 0;
-                    same = s.tag == gid;
-                    k = (int)(s.cs & 0xFFFFFFu);
-                    sm = (int64_t)(s.cs >> 24);
-                    const int rn = next_rank(own, s.rank);
-                    nk = same ? k + 1 : 1;
-                    ns = same ? sm + rn : (int64_t)rn;
-                    s.rank = rn;
-                    s.tag = gid;
-                    s.cs = ((uint64_t)ns << 24) | (uint32_t)nk;
-                    cell[c] = s;
-                }
-                if (__ballot(same)) tie = true;
-                nvalid += popc(__ballot(act && !ov));
-                // the old cell sm / k and the new one ns / nk
-                const uint64_t means = __ballot(act && (nk > 1 || k > 1));
-                if (!means) {   // both are the integers sm and ns
-#pragma unroll
-                    for (int q = 0; q < NK; ++q) {
-                        const bool a1 = act && ns <= km1[q], a0 = ov && sm <= km1[q];
-                        cK[q] += popc(__ballot(a1 && !a0)) - popc(__ballot(a0 && !a1));
-                    }
-                    // an own row: every new cell is 0; another's: old + 1, and 1 on a new column
-                    if (own) sumI -= wave_sum_i64(ov ? sm : 0);
-                    else sumI += popc(__ballot(act));
-                } else {
-                    // a quotient of integers < 2^53 is exact when it is an integer, so
-                    // trunc(q) * den == num holds for an integral cell and for no other
-                    const int kk = k > 0 ? k : 1;
-                    const int64_t oq = (int64_t)((double)sm / (double)kk);
-                    const int64_t nq = (int64_t)((double)ns / (double)nk);
-                    const bool oint = ov && oq * kk == sm;
-                    const bool ofr = ov && !oint;
-                    const bool nint = nq * nk == ns;
-                    nfrac += popc(__ballot(act && !nint && !ofr)) - popc(__ballot(act && nint && ofr));
-#pragma unroll
-                    for (int q = 0; q < NK; ++q) {
-                        const bool a1 = act && ns <= km1[q] * nk, a0 = ov && sm <= km1[q] * kk;
-                        cK[q] += popc(__ballot(a1 && !a0)) - popc(__ballot(a0 && !a1));
-                    }
-                    sumI += wave_sum_i64(act && nint ? nq : 0) - wave_sum_i64(oint ? oq : 0);
-                }
-            }
-            wave_lds_sync();
-        });
-        if (have) emit();
-        {   // the staged rows of the last, partial store
-            const int rem = (int)(nrow & 63);
-            if (lane < rem) store_row(nrow - rem + lane);
+    const int64_t n_items = a.log.n_rep * b.n_src;
+    const int64_t lo = of_first_item(n_items, blockIdx.x, gridDim.x, b.taper);
+    const int64_t hi = of_first_item(n_items, blockIdx.x + 1, gridDim.x, b.taper);
+    int64_t r_cols = -1;   // scope DF: the replica whose columns xbits / xpre hold
+    int S = 0;
+    for (int64_t it = lo; it < hi; ++it) {
+        const int64_t r = it / b.n_src;
+        const int k = (int)(it - r * b.n_src);
+        LogView v = a.log;
+        v.ctrl_idx = b.trk[k];
+        if (b.scope == RQ_LOG_OF_OWN || r != r_cols) {
+            lm_reached(v, r, w);
+            if (b.scope == RQ_LOG_OF_OWN) lm_own_columns(v, v.ctrl_idx, w);
+            S = lm_index(v, w);
+            r_cols = r;
         }
-
-        // ---- 3. counts, status and the integrals ----
-        if (lane == 0) {
-            int64_t* oc = a.out_counts + r * 4;
-            oc[0] = n_own;
-            oc[1] = n_oth;
-            oc[2] = nrow;
-            oc[3] = S;
-            a.status[r] = log_status(have, tie);
-        }
-        double* M = a.metrics + r * NV;
-        if (!have) {
-            if (lane < NV) M[lane] = __builtin_nan("");
-        } else {
-            // every row was stored by this wave: drain its stores, then order them before
-            // its loads at workgroup scope (same wave, same CU)
-            __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-            double res[NV];
-            scan_rows<NK, lm_tu(NK), RQ_LM_NL>(nrow, (double)S, a.log.end, Rt, Rs, Rv, Rc, scratch, res);
-            if (lane == 0) {
-#pragma unroll
-                for (int q = 0; q < NV; ++q) M[q] = res[q];
-            }
-        }
-        wave_lds_sync();   // the scan's scratch and the cells before the next replica's marks
+        lm_cells(S, w);
+        lm_play<NK, true>(a, v, r, it, S, w, km1);
     }
 }
 
@@ -285,6 +437,18 @@ hipError_t launch_nk(const LogMetricsArgs& a, hipStream_t s)
 {
     const size_t lds = rq_log_metrics_lds_bytes(a.log.n_sinks, a.log.n_str);
     hipLaunchKernelGGL((rq_log_metrics_k<NK>), dim3((unsigned)a.n_slots), dim3(64), lds, s, a);
+    return hipGetLastError();
+}
+
+template <int NK>
+hipError_t launch_of_nk(LogMetricsOfArgs b, hipStream_t s)
+{
+    const size_t lds = rq_log_metrics_lds_bytes(b.m.log.n_sinks, b.m.log.n_str);
+    // tapered shares only when the blocks run in several rounds: with every block resident
+    // the longest block is the launch's time
+    const int64_t resident = (int64_t)rq_occupancy(rq_log_metrics_of_k<NK>, 64, lds) * rq_cu_count();
+    b.taper = resident > 0 && b.m.n_slots > resident ? RQ_LM_OF_TAPER : 1.0;
+    hipLaunchKernelGGL((rq_log_metrics_of_k<NK>), dim3((unsigned)b.m.n_slots), dim3(64), lds, s, b);
     return hipGetLastError();
 }
 
@@ -297,6 +461,17 @@ hipError_t rq_launch_log_metrics(const LogMetricsArgs& a, hipStream_t s)
     case 2: return launch_nk<2>(a, s);
     case 3: return launch_nk<3>(a, s);
     case 4: return launch_nk<4>(a, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t rq_launch_log_metrics_of(const LogMetricsOfArgs& b, hipStream_t s)
+{
+    switch (b.m.nK) {
+    case 1: return launch_of_nk<1>(b, s);
+    case 2: return launch_of_nk<2>(b, s);
+    case 3: return launch_of_nk<3>(b, s);
+    case 4: return launch_of_nk<4>(b, s);
     }
     return hipErrorInvalidValue;
 }

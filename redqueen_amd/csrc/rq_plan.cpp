@@ -40,6 +40,7 @@ Knobs read_knobs()
     if (const char* e = getenv("RQ_RP_CHUNK")) k.rp_chunk = {true, atoi(e)};
     if (const char* e = getenv("RQ_RP_SMALL")) k.rp_small = atoi(e) != 0;
     k.clk_replay = getenv("RQ_CLK_REPLAY") != nullptr;
+    if (const char* e = getenv("RQ_LM_OF_SLOTS")) k.lm_of_slots = std::max(1, std::min(4096, atoi(e)));
     return k;
 }
 

@@ -365,4 +365,19 @@ int game_tables(const GraphTopo& g, const rq_game_player* players, int n_players
     return RQ_OK;
 }
 
+int log_of_streams(const GraphTopo& g, const int64_t* src_ids, int n_src, int* trk)
+{
+    if (!src_ids || !trk || n_src < 1 || n_src > RQ_LOG_OF_MAX_SRC) return RQ_EINVAL;
+    for (int k = 0; k < n_src; ++k) {
+        int j = -1;
+        for (int q = 0; q < g.n_str; ++q)
+            if (g.src_id[q] == src_ids[k]) j = q;
+        if (j < 0) return RQ_EINVAL;   // not a stream of the graph
+        for (int q = 0; q < k; ++q)
+            if (trk[q] == j) return RQ_EINVAL;   // named twice
+        trk[k] = j;
+    }
+    return RQ_OK;
+}
+
 }  // namespace rqh

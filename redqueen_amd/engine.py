@@ -1164,6 +1164,94 @@ class BatchResult:
                 use.cuda_stream))   # ws: allocated on `use`, reused there only
         return LogMetrics([int(k) for k in ks], metrics, counts, status)
 
+    def source_metrics(self, src_ids=None, scope="own", Ks=None, stream=None):
+        """log_metrics for any sources of the graph (rq_log_metrics_of): the reference's
+        time_in_top_k(df, K, src_id=c), average_rank(df, src_id=c) and int_r_2 for every
+        c of ``src_ids`` -- default the result's ``player_ids`` when it has them, else
+        every source of the graph.  ``scope`` "df": on the replica's whole dataframe;
+        "own": on df[df.sink_id.isin(followers of c)], the feeds an Opt tracks its rank
+        on.  Returns a ``SourceMetrics`` of device tensors: ``metrics`` [R, P, nK + 2],
+        ``counts`` [R, P, 4] (c's events with a row, the others', pivot rows, pivot
+        columns) and ``status`` [R, P].  Sources go in chunks of LOG_OF_MAX_SRC, replicas
+        in chunks that keep the workspace within LOG_METRICS_WS_BYTES.  Raises as
+        log_metrics does; needs event_log=True."""
+        g = self._log_graph()
+        ks = self._log_ks(Ks)
+        if scope not in ("df", "own"):
+            raise ValueError('source_metrics: scope "df" or "own" expected')
+        if src_ids is None:
+            src_ids = getattr(self, "player_ids", None) or g.stream_src_ids
+        ids = _arr(src_ids, np.int64).reshape(-1)
+        known = set(int(s) for s in g.stream_src_ids)
+        if ids.size < 1 or len(set(ids.tolist())) != ids.size or not set(ids.tolist()) <= known:
+            raise ValueError("source_metrics: distinct sources of the graph expected")
+        if not all(L.has(fn) for fn in L.OPTIONAL):
+            raise L.RQError("rq_log_metrics_of", L.RQ_EUNSUPPORTED)
+        use = stream or torch.cuda.current_stream()
+        with torch.cuda.stream(use):
+            return self._source_metrics(ids, L.LOG_OF_OWN if scope == "own" else L.LOG_OF_DF, ks, use)
+
+    def _source_metrics(self, ids, scope, ks, use):
+        g, lib = self.graph, L.lib()
+        dev = self.ev_t.device
+        R, cap = self.ev_t.shape
+        P, nK = ids.size, ks.size
+        nb = C.c_size_t()
+        out = SourceMetrics([int(s) for s in ids], [int(k) for k in ks],
+                            torch.empty((R, P, nK + 2), dtype=torch.float64, device=dev),
+                            torch.empty((R, P, 4), dtype=torch.int64, device=dev),
+                            torch.empty((R, P), dtype=torch.int32, device=dev))
+        if R == 0 or cap == 0:   # nothing to play: every (replica, source) is empty
+            L.check("rq_log_metrics_of_workspace", lib.rq_log_metrics_of_workspace(g._h, 1, 1, 1, nK, C.byref(nb)))
+            out.metrics.fill_(float("nan"))
+            out.counts.zero_()
+            out.status.fill_(L.ST_EMPTY)
+            return out
+        ws = None
+        for p0 in range(0, P, L.LOG_OF_MAX_SRC):
+            sub = np.ascontiguousarray(ids[p0:p0 + L.LOG_OF_MAX_SRC])
+            n_src = sub.size
+            # the whole batch in one launch if its workspace (which stops growing at a fixed
+            # number of blocks) fits the budget, else as many replicas a call as fit it
+            chunk = R
+            L.check("rq_log_metrics_of_workspace",
+                    lib.rq_log_metrics_of_workspace(g._h, n_src, R, cap, nK, C.byref(nb)))
+            if nb.value > self.LOG_METRICS_WS_BYTES:
+                L.check("rq_log_metrics_of_workspace",
+                        lib.rq_log_metrics_of_workspace(g._h, 1, 1, cap, nK, C.byref(nb)))
+                chunk = max(1, min(R, self.LOG_METRICS_WS_BYTES // nb.value // n_src))
+                L.check("rq_log_metrics_of_workspace",
+                        lib.rq_log_metrics_of_workspace(g._h, n_src, chunk, cap, nK, C.byref(nb)))
+            if ws is None or ws.numel() < nb.value:
+                ws = torch.empty(max(256, nb.value), dtype=torch.uint8, device=dev)
+            whole = n_src == P
+            for lo in range(0, R, chunk):
+                n = min(chunk, R - lo)
+                # a chunk of the sources writes its own [n, n_src, ...] block, copied into place
+                m, c, s = ((out.metrics[lo:], out.counts[lo:], out.status[lo:]) if whole else
+                           (torch.empty((n, n_src, nK + 2), dtype=torch.float64, device=dev),
+                            torch.empty((n, n_src, 4), dtype=torch.int64, device=dev),
+                            torch.empty((n, n_src), dtype=torch.int32, device=dev)))
+                L.check("rq_log_metrics_of", lib.rq_log_metrics_of(
+                    g._h, sub.ctypes.data_as(L._pi64), n_src, scope, self.ev_t[lo:].data_ptr(),
+                    self.ev_src[lo:].data_ptr(), self.counts[lo:].data_ptr(), n, cap,
+                    ks.ctypes.data_as(L._pi32), nK, m.data_ptr(), c.data_ptr(), s.data_ptr(),
+                    ws.data_ptr(), ws.numel(), use.cuda_stream))   # ws: allocated on `use`, reused there only
+                if not whole:
+                    out.metrics[lo:lo + n, p0:p0 + n_src] = m
+                    out.counts[lo:lo + n, p0:p0 + n_src] = c
+                    out.status[lo:lo + n, p0:p0 + n_src] = s
+        return out
+
+    def player_metrics(self, scope="own", Ks=None, stream=None):
+        """source_metrics of the game's players (``player_ids``, in their order): how
+        visible every competing Opt ended up, on its own followers' feeds (scope "own") or
+        on the whole dataframe ("df").  ValueError for a result without players."""
+        ids = getattr(self, "player_ids", None)
+        if not ids:
+            raise ValueError("player_metrics: the result of a game (Opt broadcasters among the sources) expected")
+        return self.source_metrics(ids, scope=scope, Ks=Ks, stream=stream)
+
     def events(self, i):
         """(t, src_id) numpy arrays of replica i (needs event_log=True)."""
         n = int(self.counts[i, 2].item())
@@ -1191,6 +1279,28 @@ class LogMetrics:
     @property
     def r_2(self):
         return self.metrics[:, len(self.Ks) + 1]
+
+
+class SourceMetrics:
+    """BatchResult.source_metrics' outputs for the sources ``src_ids`` [P]: ``metrics``
+    [R, P, nK + 2] (top_K..., avg_rank, r_2), ``counts`` [R, P, 4] (the source's events
+    with a row, the other sources', pivot rows, pivot columns) and ``status`` [R, P] (0,
+    ST_TIE: informational, or ST_EMPTY: metrics NaN), device tensors."""
+
+    def __init__(self, src_ids, Ks, metrics, counts, status):
+        self.src_ids, self.Ks = src_ids, Ks
+        self.metrics, self.counts, self.status = metrics, counts, status
+
+    def top_k(self, k):
+        return self.metrics[:, :, self.Ks.index(k)]
+
+    @property
+    def avg_rank(self):
+        return self.metrics[:, :, len(self.Ks)]
+
+    @property
+    def r_2(self):
+        return self.metrics[:, :, len(self.Ks) + 1]
 
 
 class Timeline:
