@@ -348,6 +348,27 @@ int rq_metrics_replay_batch(const double* t, const int64_t* src, const int64_t* 
                             int64_t n_rows, int64_t src_id, double end_time, const int32_t* Ks,
                             int32_t nK, double* out, int64_t* counts, void* workspace,
                             size_t workspace_bytes, void* hip_stream);
+/* The same on dataframes in ANY row order, as the reference's functions take them
+ * (utils.py:41: the is_sorted assertion is commented out): a concat of two runs, a
+ * shuffle, re-appended rows.  Ranks are taken per sink in DATAFRAME order, the pivot is
+ * on the sorted unique t with the mean of duplicate (t, sink) rows, and the two event
+ * counts are distinct-id counts whatever the order of the ids -- sorting the rows by t
+ * first gives other numbers.  Arguments, outputs and per-dataframe statuses are those of
+ * rq_metrics_replay_batch (df_off NULL: one dataframe of n_rows rows), except that a
+ * dataframe whose 't' decreases is evaluated instead of flagged RQ_EUNSORTED, with any
+ * number of unique sinks; its event counts do not need increasing ids.  A dataframe in
+ * time order takes the tiers of rq_metrics_replay_batch for `flags` and returns its bits.
+ * Still RQ_EUNSORTED (NaN metrics): a dataframe whose 't' decreases AND holds a NaN (the
+ * reference drops such rows in its pivot).
+ * Workspace: rq_replay_unsorted_workspace_size = the replay workspace for `flags`
+ * followed by the sort area (64 B per row).  One workgroup sorts one unsorted dataframe.
+ * No ABI version change: detect the entries by symbol. */
+int rq_replay_unsorted_workspace_size(int64_t n_rows, int64_t n_df, int32_t nK, int32_t flags, size_t* bytes);
+int rq_metrics_replay_unsorted(const double* t, const int64_t* src, const int64_t* sink,
+                               const int64_t* event_id, const int64_t* df_off /* NULL: one df */,
+                               int64_t n_df, int64_t n_rows, int64_t src_id, double end_time,
+                               const int32_t* Ks, int32_t nK, double* out, int64_t* counts,
+                               void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /* Offline oracle (utils.oracle_ranking) for n_inst single-follower walls at once.
  * Instance i: n_i wall events, w_i[0..n_i+2) = np.diff([0, 0, event_times..., end_time])

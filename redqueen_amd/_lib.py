@@ -130,6 +130,8 @@ class RQError(RuntimeError):
 _lib = None
 # entries added without an ABI version change that lib() does not insist on
 OPTIONAL = ("rq_log_metrics_of_workspace", "rq_log_metrics_of")
+# the replay of dataframes in any row order (utils.replay_columns(unsorted="sort")), optional likewise
+OPTIONAL_UNSORTED = ("rq_replay_unsorted_workspace_size", "rq_metrics_replay_unsorted")
 
 
 def has(fn):
@@ -209,6 +211,11 @@ def lib():
         L.rq_log_metrics_of.argtypes = [_P, _pi64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, C.c_int64,
                                         _pi32, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]
         L.rq_log_metrics_of.restype = C.c_int
+    if all(hasattr(L, fn) for fn in OPTIONAL_UNSORTED):
+        L.rq_replay_unsorted_workspace_size.argtypes = L.rq_replay_workspace_size.argtypes
+        L.rq_replay_unsorted_workspace_size.restype = C.c_int
+        L.rq_metrics_replay_unsorted.argtypes = L.rq_metrics_replay_batch.argtypes
+        L.rq_metrics_replay_unsorted.restype = C.c_int
     L.rq_timing.argtypes = [C.c_int]
     L.rq_timing_read.argtypes = [_pd, _pi64]
     for fn in ("rq_timing", "rq_timing_read", "rq_graph_build", "rq_graph_free", "rq_graph_info", "rq_graph_source_ids",
@@ -262,7 +269,8 @@ def check(fn, code):
 EXPORTED = ["rq_abi_version", "rq_strerror", "rq_graph_build", "rq_graph_free", "rq_graph_info",
             "rq_graph_source_ids", "rq_graph_followers", "rq_workspace_size",
             "rq_event_capacity", "rq_plan_info", "rq_plan_info_n", "rq_run_batch", "rq_replay_workspace_size",
-            "rq_metrics_replay", "rq_metrics_replay_batch", "rq_oracle_workspace_size", "rq_oracle_dp", "rq_rank_table",
+            "rq_metrics_replay", "rq_metrics_replay_batch", "rq_replay_unsorted_workspace_size",
+            "rq_metrics_replay_unsorted", "rq_oracle_workspace_size", "rq_oracle_dp", "rq_rank_table",
             "rq_u_int", "rq_log_rows", "rq_log_expand", "rq_log_timeline", "rq_log_followers",
             "rq_log_followers_tiled_workspace", "rq_log_followers_tiled",
             "rq_log_rank_hist", "rq_log_metrics_workspace", "rq_log_metrics",

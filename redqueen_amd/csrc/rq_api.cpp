@@ -812,10 +812,32 @@ RpPlan rp_plan(int64_t n_rows, int64_t n_df, int32_t nK)
     return p;
 }
 
+// the sort area of rq_metrics_replay_unsorted, behind the replay workspace: the radix
+// sort's scratch (RP_US_SCRATCH B per row) and the t-ordered columns (24 B per row)
+struct RpSortPlan {
+    size_t off_scratch, off_t, off_col, off_rank, off_prev, off_g, bytes;
+};
+RpSortPlan rp_sort_plan(int64_t n_rows)
+{
+    RpSortPlan p{};
+    const size_t A = 256, n = (size_t)std::max<int64_t>(n_rows, 1);
+    size_t o = 0;
+    p.off_scratch = o; o = align_up(o + RP_US_SCRATCH * n, A);
+    p.off_t = o;       o = align_up(o + 8 * n, A);
+    p.off_col = o;     o = align_up(o + 4 * n, A);
+    p.off_rank = o;    o = align_up(o + 4 * n, A);
+    p.off_prev = o;    o = align_up(o + 4 * n, A);
+    p.off_g = o;       o = align_up(o + 4 * n, A);
+    p.bytes = o;
+    return p;
+}
+
+// sort_area: null, or the sort area (rp_sort_plan) -- dataframes whose t decreases are
+// then evaluated by the sort route instead of being flagged RQ_EUNSORTED
 int rp_run(const double* t, const int64_t* src, const int64_t* sink, const int64_t* event_id,
            const int64_t* df_off, int64_t n_df, int64_t n_rows, int64_t src_id, double end_time,
            const int32_t* Ks, int32_t nK, double* out, int64_t* counts, void* workspace,
-           size_t workspace_bytes, void* hip_stream)
+           size_t workspace_bytes, void* hip_stream, char* sort_area = nullptr)
 {
     if (!out || !counts || !workspace || !Ks || n_df < 1 || n_rows < 0) return RQ_EINVAL;
     if (n_rows > 0 && (!t || !src || !sink)) return RQ_EINVAL;
@@ -873,6 +895,15 @@ int rp_run(const double* t, const int64_t* src, const int64_t* sink, const int64
         a.carry = (RcCarry*)(cw + p.c_carry);
         a.state = (RcState*)(cw + p.c_state);
     }
+    if (sort_area) {
+        const RpSortPlan sp = rp_sort_plan(n_rows);
+        a.us_scratch = sort_area + sp.off_scratch;
+        a.us_t = (double*)(sort_area + sp.off_t);
+        a.us_col = (int*)(sort_area + sp.off_col);
+        a.us_rank = (int*)(sort_area + sp.off_rank);
+        a.us_prev = (int*)(sort_area + sp.off_prev);
+        a.us_g = (int*)(sort_area + sp.off_g);
+    }
     hipStream_t s = (hipStream_t)hip_stream;
     {
         TimedLaunch tl(K_REPLAY, s);
@@ -882,6 +913,9 @@ int rp_run(const double* t, const int64_t* src, const int64_t* sink, const int64
         if (large && rq_launch_rp(a, RP_PHASE_GLOBAL, s) != hipSuccess) return RQ_EHIP;
         if (rq_launch_rp(a, RP_PHASE_KEYS, s) != hipSuccess) return RQ_EHIP;
         if (rq_launch_rp(a, RP_PHASE_SEQ, s) != hipSuccess) return RQ_EHIP;
+        // always launched (no host read of the flags): workgroups of sorted dataframes leave at once
+        if (sort_area && rq_launch_rp_sort(a, s) != hipSuccess) return RQ_EHIP;
+        if (sort_area && rq_launch_rp(a, RP_PHASE_SEQ_GIVEN, s) != hipSuccess) return RQ_EHIP;
     }
     TimedLaunch tl(K_SCAN, s);
     return rq_launch_rp(a, RP_PHASE_SCAN, s) == hipSuccess ? RQ_OK : RQ_EHIP;
@@ -914,6 +948,37 @@ int rq_metrics_replay_batch(const double* t, const int64_t* src, const int64_t* 
     if (!df_off) return RQ_EINVAL;
     return rp_run(t, src, sink, event_id, df_off, n_df, n_rows, src_id, end_time, Ks, nK, out,
                   counts, workspace, workspace_bytes, hip_stream);
+}
+
+int rq_replay_unsorted_workspace_size(int64_t n_rows, int64_t n_df, int32_t nK, int32_t flags, size_t* bytes)
+{
+    size_t base = 0;
+    const int rc = rq_replay_workspace_size(n_rows, n_df, nK, flags, &base);
+    if (rc != RQ_OK) return rc;
+    *bytes = base + rp_sort_plan(n_rows).bytes;
+    return RQ_OK;
+}
+
+int rq_metrics_replay_unsorted(const double* t, const int64_t* src, const int64_t* sink,
+                               const int64_t* event_id, const int64_t* df_off, int64_t n_df,
+                               int64_t n_rows, int64_t src_id, double end_time, const int32_t* Ks,
+                               int32_t nK, double* out, int64_t* counts, void* workspace,
+                               size_t workspace_bytes, void* hip_stream)
+{
+    if (!workspace || n_rows < 0 || n_df < 1 || nK < 1 || nK > RQ_MAX_K) return RQ_EINVAL;
+    if (!df_off && n_df != 1) return RQ_EINVAL;
+    // the replay workspace for the layout the caller asked for (the largest that fits with the
+    // sort area behind it), of exactly that size: the sorted dataframes take the tiers and
+    // return the bits of rq_metrics_replay_batch
+    const RpPlan p = rp_plan(n_rows, n_df, nK);
+    const size_t sort_bytes = rp_sort_plan(n_rows).bytes;
+    const size_t layouts[4] = {p.large + p.chunk, p.large, p.small + p.chunk, p.small};
+    for (size_t base : layouts) {
+        if (workspace_bytes < base + sort_bytes) continue;
+        return rp_run(t, src, sink, event_id, df_off, n_df, n_rows, src_id, end_time, Ks, nK, out,
+                      counts, workspace, base, hip_stream, (char*)workspace + base);
+    }
+    return RQ_EINVAL;
 }
 
 }  // extern "C"

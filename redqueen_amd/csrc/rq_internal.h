@@ -254,10 +254,12 @@ struct RpInfo {
 #define RP_EMPTYDF 32    // no rows
 #define RP_BADOFF 64     // df_off[d] .. df_off[d + 1] is not a valid row range (< 2^31 rows)
 #define RP_MID 256       // more unique sinks than the small LDS table: the full-table pass takes it
+#define RP_SORTED 512    // the sort route (rq_replay_sort.hip) evaluated an unsorted df: its rows, dense
+                         // columns and ranks stand in t order in the sort area (RpArgs::us_*)
 #define RP_CSKIP 128     // chunked mode: the df is not chunkable (> RC_S sinks, the INT64_MIN id):
                          // the one-workgroup path (rq_rp_fast) takes it
 enum { RP_PHASE_FAST = 0, RP_PHASE_GLOBAL = 1, RP_PHASE_KEYS = 2, RP_PHASE_SEQ = 3, RP_PHASE_SCAN = 4,
-       RP_PHASE_CHUNK = 5, RP_PHASE_SMALL = 6 };
+       RP_PHASE_CHUNK = 5, RP_PHASE_SMALL = 6, RP_PHASE_SEQ_GIVEN = 7 };
 // chunked replay (one dataframe over many workgroups): rows per chunk, most unique sinks
 // per dataframe, hash slots per dataframe
 #define RC_L 4096
@@ -310,8 +312,22 @@ struct RpArgs {
     RcCarry* carry;
     RcState* state;
     unsigned long long* clk;  // RQ_PHASE_CLOCK builds only: rq_rp_fast per-phase s_memtime sums [8]
+    // sort route (rq_metrics_replay_unsorted; null otherwise).  us_scratch: RP_US_SCRATCH bytes per
+    // row, dataframe d's at byte RP_US_SCRATCH * df_off[d]: the radix sort's key / payload
+    // ping-pong and per-row column / rank, later the given-rank rq_rp_seq's per-sink state.
+    // The rest [n_rows], dataframe d's rows in (t, dataframe index) order at df_off[d]:
+    // t, dense column, rank, previous rank of the sink (-1: none), pivot row.
+    char* us_scratch;
+    double* us_t;
+    int* us_col;
+    int* us_rank;
+    int* us_prev;
+    int* us_g;
 };
+#define RP_US_SCRATCH 40
 hipError_t rq_launch_rp(const RpArgs& a, int phase, hipStream_t s);
+// the unsorted route for the dataframes rq_rp_fast flagged RP_UNSORTED (rq_replay_sort.hip)
+hipError_t rq_launch_rp_sort(const RpArgs& a, hipStream_t s);
 
 // ---- analysis kernels (rq_analysis.hip) ----
 struct OracleArgs {

@@ -783,23 +783,29 @@ __global__ __launch_bounds__(RP_B) void rq_rp_keys(RpArgs a)
 // rq_rp_seq: the exact sequential replay of one dataframe per wavefront, for
 // the dataframes with pivot means (duplicate (t, sink) rows).  Per-sink state in
 // LDS when it fits (40 B per sink), else in the large workspace.
+// GIVEN: the instance for the sort route's dataframes (RP_SORTED, rq_replay_sort.hip).
+// Its rows are the sort area's, in (t, dataframe index) order, each with its dense
+// column and its rank (taken in dataframe order, so not recomputed here); per-sink
+// state past the LDS limit lives in the sort scratch (40 B per row >= 40 B per sink).
 // ============================================================================
 constexpr size_t RP_SEQ_LDS = 120 * 1024;
+static_assert(RP_US_SCRATCH >= 40, "rq_rp_seq's per-sink state");
 
-template <int NK>
+template <int NK, bool GIVEN = false>
 __global__ __launch_bounds__(64) void rq_rp_seq(RpArgs a)
 {
     const int64_t d = blockIdx.x;
     RpInfo* inf = a.info + d;
     const int fl = inf->flags;
     if (!(fl & RP_FALLBACK) || (fl & (RP_UNSORTED | RP_GLOBAL | RP_BIG))) return;
+    if (GIVEN != ((fl & RP_SORTED) != 0)) return;
     extern __shared__ double lds_rp[];
     const int lane = lane_id();
     const int64_t r0 = df_begin(a, d), r1 = df_end(a, d);
     const int64_t n_rows = r1 - r0;
     const int S = inf->S;
     const int64_t* keys = a.keys + r0;
-    const double* T = a.t + r0;
+    const double* T = (GIVEN ? a.us_t : a.t) + r0;
     const int64_t* SRC = a.src + r0;
     const int64_t* SNK = a.sink + r0;
 
@@ -807,6 +813,8 @@ __global__ __launch_bounds__(64) void rq_rp_seq(RpArgs a)
     char* base;
     if ((size_t)S * 40 <= RP_SEQ_LDS) {
         base = reinterpret_cast<char*>(lds_rp + npsum_lds_doubles<1>());
+    } else if (GIVEN) {
+        base = a.us_scratch + (size_t)RP_US_SCRATCH * (size_t)r0;
     } else {
         if (!a.gstate) {
             if (lane == 0) atomicOr(&inf->flags, RP_BIG);
@@ -941,9 +949,15 @@ __global__ __launch_bounds__(64) void rq_rp_seq(RpArgs a)
         const int64_t i = i0 + lane;
         const bool valid = i < n_rows;
         const double ti = valid ? T[i] : RQ_INF;
-        const int64_t si = valid ? SRC[i] : 0;
+        const int64_t si = valid && !GIVEN ? SRC[i] : 0;
         int ci = 0;
-        if (valid) {   // column = rank of the sink id among the sorted unique ids
+        int ri = 0;    // GIVEN: the row's rank
+        if (GIVEN) {
+            if (valid) {
+                ci = a.us_col[r0 + i];
+                ri = a.us_rank[r0 + i];
+            }
+        } else if (valid) {   // column = rank of the sink id among the sorted unique ids
             const int64_t k = SNK[i];
             int lo = 0, hi = S;
             while (lo < hi) {
@@ -976,10 +990,13 @@ __global__ __launch_bounds__(64) void rq_rp_seq(RpArgs a)
                 __builtin_amdgcn_wave_barrier();
                 const bool lead = pend && ctag[ci] == lane;
                 if (lead) {
-                    const int p = pos[ci] + 1;
-                    pos[ci] = p;
-                    if (si == a.src_id) last[ci] = p;
-                    const int r = p - last[ci];
+                    int r = ri;
+                    if (!GIVEN) {
+                        const int p = pos[ci] + 1;
+                        pos[ci] = p;
+                        if (si == a.src_id) last[ci] = p;
+                        r = p - last[ci];
+                    }
                     if (gtag[ci] != group) {
                         gtag[ci] = group;
                         gsum[ci] = 0.0;
@@ -1794,6 +1811,11 @@ hipError_t rp_launch_t(const RpArgs& a, int phase, hipStream_t s)
     case RP_PHASE_SEQ: {
         const size_t lds = npsum_lds_doubles<1>() * sizeof(double) + RP_SEQ_LDS;
         hipLaunchKernelGGL((rq_rp_seq<NK>), dim3(nd), dim3(64), lds, s, a);
+        break;
+    }
+    case RP_PHASE_SEQ_GIVEN: {
+        const size_t lds = npsum_lds_doubles<1>() * sizeof(double) + RP_SEQ_LDS;
+        hipLaunchKernelGGL((rq_rp_seq<NK, true>), dim3(nd), dim3(64), lds, s, a);
         break;
     }
     case RP_PHASE_CHUNK: {

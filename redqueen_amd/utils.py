@@ -62,7 +62,31 @@ def torch_empty_u8(n, dev):
     return torch.empty(max(256, int(n)), dtype=torch.uint8, device=dev)
 
 
-def replay_columns(t, src, sink, eid=None, df_off=None, src_id=0, end_time=0.0, Ks=(1,), chunked=None):
+class accept_unsorted(object):
+    """Module switch for the single-dataframe functions (replay_metrics, time_in_top_k,
+    average_rank, int_r_2, num_tweets_of, add_perf): with it on they evaluate a dataframe
+    in any row order as the reference does (ranks per sink in dataframe order, pivot on
+    the sorted unique t; rq_metrics_replay_unsorted) instead of raising RQ_EUNSORTED.
+
+        utils.accept_unsorted(True)            # on until accept_unsorted(False)
+        with utils.accept_unsorted(True): ...  # on inside the block, restored after it
+    """
+    enabled = False
+
+    def __init__(self, on=True):
+        self._old = accept_unsorted.enabled
+        accept_unsorted.enabled = bool(on)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        accept_unsorted.enabled = self._old
+        return False
+
+
+def replay_columns(t, src, sink, eid=None, df_off=None, src_id=0, end_time=0.0, Ks=(1,), chunked=None,
+                   unsorted="reject"):
     """rq_metrics_replay(_batch) on device columns (torch tensors: t f64, src / sink /
     event_id i64, df_off i64 [n_df + 1] or None for one dataframe).  Sink ids are raw:
     the pivot columns are built on the device.  Returns (metrics [n_df, nK + 2],
@@ -70,9 +94,16 @@ def replay_columns(t, src, sink, eid=None, df_off=None, src_id=0, end_time=0.0, 
     (RQ_EUNSORTED).  Dataframes wider than the LDS tables are rerun with the large
     workspace, as the engine reruns overflowing replicas.  ``chunked``: None = give
     few long dataframes the chunked (many-workgroup) replay's workspace; True / False
-    = always / never (A/B; the library then picks the path, env RQ_RP_CHUNK forces it)."""
+    = always / never (A/B; the library then picks the path, env RQ_RP_CHUNK forces it).
+    ``unsorted``: "reject" flags a dataframe whose t decreases RQ_EUNSORTED; "sort"
+    evaluates it in its row order as the reference does (rq_metrics_replay_unsorted)."""
     import torch
     from . import _lib as L
+    if unsorted not in ("reject", "sort"):
+        raise ValueError("unsorted must be 'reject' or 'sort', not %r" % (unsorted,))
+    sort = unsorted == "sort"
+    if sort and not all(L.has(fn) for fn in L.OPTIONAL_UNSORTED):
+        raise RuntimeError("this librq.so has no rq_metrics_replay_unsorted")
     dev = t.device
     n = int(t.numel())
     n_df = 1 if df_off is None else int(df_off.numel()) - 1
@@ -87,14 +118,21 @@ def replay_columns(t, src, sink, eid=None, df_off=None, src_id=0, end_time=0.0, 
     f0 = L.REPLAY_CHUNKED if chunked else 0
     for flags in (f0, f0 | L.REPLAY_LARGE):
         nbytes = C.c_size_t()
-        L.check("rq_replay_workspace_size",
-                lib.rq_replay_workspace_size(n, n_df, Ks.size, flags, C.byref(nbytes)))
+        if sort:
+            L.check("rq_replay_unsorted_workspace_size",
+                    lib.rq_replay_unsorted_workspace_size(n, n_df, Ks.size, flags, C.byref(nbytes)))
+        else:
+            L.check("rq_replay_workspace_size",
+                    lib.rq_replay_workspace_size(n, n_df, Ks.size, flags, C.byref(nbytes)))
         ws = _replay_ws(dev, nbytes.value)
         ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None  # noqa: E731
         args = (ptr(t), ptr(src), ptr(sink), ptr(eid))
         tail = (int(src_id), float(end_time), Ks.ctypes.data_as(L._pi32), Ks.size,
                 out.data_ptr(), cnt.data_ptr(), ws.data_ptr(), ws.numel(), st)
-        if df_off is None:
+        if sort:
+            L.check("rq_metrics_replay_unsorted", lib.rq_metrics_replay_unsorted(
+                *args, df_off.data_ptr() if df_off is not None else None, n_df, n, *tail))
+        elif df_off is None:
             L.check("rq_metrics_replay", lib.rq_metrics_replay(*args, n, *tail))
         else:
             L.check("rq_metrics_replay_batch",
@@ -117,7 +155,8 @@ def replay_metrics(df, src_id, end_time, Ks=(1,)):
         return torch.from_numpy(np.ascontiguousarray(df[name].values, dtype=np.int64)).to(dev)
     tt = torch.from_numpy(np.ascontiguousarray(df["t"].values, dtype=np.float64)).to(dev)
     te = col("event_id") if "event_id" in df.columns else None
-    o, c = replay_columns(tt, col("src_id"), col("sink_id"), te, None, src_id, end_time, Ks)
+    o, c = replay_columns(tt, col("src_id"), col("sink_id"), te, None, src_id, end_time, Ks,
+                          unsorted="sort" if accept_unsorted.enabled else "reject")
     o = o[0].cpu().numpy()
     c = c[0].cpu().numpy()
     nK = len(Ks)
@@ -131,10 +170,10 @@ def replay_metrics(df, src_id, end_time, Ks=(1,)):
             "rows": int(c[2]), "cols": int(c[3])}
 
 
-def replay_frames(dfs, src_id, end_time, Ks=(1,)):
+def replay_frames(dfs, src_id, end_time, Ks=(1,), unsorted="reject"):
     """Metrics of many dataframes (the reference's per-replica utils calls) in one
     batched replay: a pandas DataFrame with top_K..., avg_rank, r_2, num_events,
-    world_events per input df."""
+    world_events per input df.  ``unsorted``: as replay_columns."""
     import pandas as pd
     import torch
     cols = ["top_" + str(k) for k in Ks] + ["avg_rank", "r_2", "num_events", "world_events",
@@ -157,7 +196,7 @@ def replay_frames(dfs, src_id, end_time, Ks=(1,)):
             np.concatenate([d[name].values for d in dfs]) if len(dfs) else np.zeros(0), dtype=dt)).to(dev)
     eid = cat("event_id", np.int64) if all(has_eid) else None
     o, c = replay_columns(cat("t", np.float64), cat("src_id", np.int64), cat("sink_id", np.int64),
-                          eid, off, src_id, end_time, Ks)
+                          eid, off, src_id, end_time, Ks, unsorted=unsorted)
     o, c = o.cpu().numpy(), c.cpu().numpy()
     res = {("top_" + str(k)): o[:, i] for i, k in enumerate(Ks)}
     res.update(avg_rank=o[:, len(Ks)], r_2=o[:, len(Ks) + 1], num_events=c[:, 0],

@@ -8,6 +8,8 @@
   * rq_scan: 24 B read per pivot row (timed inside the plain C3 run)
   * rq_metrics_replay_batch on the 256 exported C3 dataframes (24 B read per df row,
     32 B with event ids) and rq_metrics_replay on one df through the pandas facade
+  * rq_metrics_replay_unsorted (replay_unsorted): one exported C3 dataframe shuffled, and
+    the 256 with their halves swapped, beside the sorted replay of the same rows
   * rq_oracle_dp: n = 8000 walls, 64 instances
   * the exact sequential sweep (the fallback for multigraphs and repeated RealData
     times): the C3 network with duplicated edges, a 600-source world, C3 with a
@@ -37,11 +39,11 @@ from redqueen_amd import engine, graphs, utils  # noqa: E402
 PEAK = 8000.0
 SECTIONS = ["sweep_event_log", "log_expand", "scan", "replay_batch", "replay_batch_eid", "replay_batch_1024",
             "replay_batch_eid_chunked", "replay_one_df", "replay_one_df_one_workgroup",
-            "replay_one_df_facade", "oracle_dp", "seq_multigraph_c3", "seq_600_sources",
+            "replay_one_df_facade", "replay_unsorted", "oracle_dp", "seq_multigraph_c3", "seq_600_sources",
             "seq_max_events_c3", "fast_max_events_c3", "fast_realdata_c3", "fast_600_sources",
             "fast_3000_sources"]
 REPLAY = {"log_expand", "replay_batch", "replay_batch_eid", "replay_batch_1024", "replay_batch_eid_chunked",
-          "replay_one_df", "replay_one_df_one_workgroup", "replay_one_df_facade"}
+          "replay_one_df", "replay_one_df_one_workgroup", "replay_one_df_facade", "replay_unsorted"}
 
 
 def timed(fn, reps=3):
@@ -171,6 +173,62 @@ def replay(g, so, a, res, want):
         _, ms, wall = timed(lambda: utils.replay_metrics(df, so["src_id"], so["end_time"], (1,)), a.reps)
         res["replay_one_df_facade"] = {"rows": len(df), "ms": ms[3] + ms[2], "wall_ms": wall * 1e3,
                                        "GBps": 32 * len(df) / (ms[3] + ms[2]) / 1e6}
+    if want("replay_unsorted"):
+        if all(L.has(fn) for fn in L.OPTIONAL_UNSORTED):
+            replay_unsorted(cols, ro, so, a, res)
+        else:   # an A/B library from before the entry
+            res["replay_unsorted"] = {"skipped": "librq.so has no rq_metrics_replay_unsorted"}
+
+
+def replay_unsorted(cols, ro, so, a, res):
+    """The sort route (one workgroup sorts one dataframe) beside the sorted replay of the
+    same rows, which is its floor: one dataframe shuffled; 256 with their halves swapped."""
+    def run(c, off, unsorted, **kw):
+        (m, cn), ms, wall = timed(lambda: utils.replay_columns(
+            c["t"], c["src_id"], c["sink_id"], c["event_id"], off, so["src_id"], so["end_time"], (1,),
+            unsorted=unsorted, **kw), a.reps)
+        return m, cn, ms[3] + ms[2], wall * 1e3
+
+    def entry(n, floor_ms, ms, wall, cn, extra):
+        d = {"rows": n, "ms": ms, "wall_ms": wall, "rows_per_s": n / ms * 1e3,
+             "sorted_ms": floor_ms, "sorted_rows_per_s": n / floor_ms * 1e3, "ratio": ms / floor_ms,
+             "all_evaluated": bool((cn[:, 2] > 0).all().item())}
+        d.update(extra)
+        return d
+    out = {"build": L.build_stamp()}
+    # one dataframe, its rows shuffled
+    a0, a1 = int(ro[0]), int(ro[1])
+    one = {k: v[a0:a1].contiguous() for k, v in cols.items()}
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    perm = torch.randperm(a1 - a0, generator=gen, device="cuda")
+    shuf = {k: v[perm].contiguous() for k, v in one.items()}
+    m0, c0, floor, _ = run(one, None, "reject")
+    os.environ["RQ_RP_CHUNK"] = "0"   # the sorted replay in ONE workgroup, as the sort route runs
+    _, _, floor1, _ = run(one, None, "reject", chunked=False)
+    del os.environ["RQ_RP_CHUNK"]
+    m1, c1, ms, wall = run(shuf, None, "sort")
+    ms_same = run(one, None, "sort")[2]
+    out["one_df_shuffled"] = entry(a1 - a0, floor, ms, wall, c1, {
+        "sorted_one_workgroup_ms": floor1, "sorted_rows_through_unsorted_entry_ms": ms_same,
+        "pivot_rows": int(c1[0, 2].item()), "sinks": int(c1[0, 3].item())})
+    del shuf, perm, one
+    # every dataframe with its halves swapped: t decreases once per dataframe, and a sink's
+    # rows change their order, so ranks differ from the sorted frame's
+    n = int(ro[-1])
+    idx = np.empty(n, dtype=np.int64)
+    for d in range(len(ro) - 1):
+        r0, r1 = int(ro[d]), int(ro[d + 1])
+        h = (r0 + r1) // 2
+        idx[r0:r0 + (r1 - h)] = np.arange(h, r1)
+        idx[r0 + (r1 - h):r1] = np.arange(r0, h)
+    off = torch.from_numpy(ro).cuda()
+    tidx = torch.from_numpy(idx).cuda()
+    m0, c0, floor, _ = run(cols, off, "reject")
+    swapped = {k: v[tidx].contiguous() for k, v in cols.items()}
+    del tidx
+    m1, c1, ms, wall = run(swapped, off, "sort")
+    out["halves_swapped_%d" % (len(ro) - 1)] = entry(n, floor, ms, wall, c1, {"dataframes": len(ro) - 1})
+    res["replay_unsorted"] = out
 
 
 def oracle(a, res):
