@@ -198,7 +198,7 @@ typedef struct rq_batch_desc {
                                     tiles, per-replica RealData streams play on them (a replica
                                     meeting equal times is flagged RQ_ST_TIE); the fast sweeps
                                     write the event log themselves.
-                                    The fast sweeps play MERGED streams: rq_gen_streams writes
+                                    The fast sweeps play MERGED streams: rq_gen_classes writes
                                     every source's arrivals, rq_merge_streams merges them into
                                     one (t, stream) sequence per replica, and the sweep plays it
                                     in tiles of 64 entries (the fused sweep for <= 64 sources,

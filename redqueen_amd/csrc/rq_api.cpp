@@ -173,7 +173,7 @@ struct rq_graph : GraphTopo {
     DevBuf<int> d_csr_col_el, d_lay_ptr, d_lay_end;
     DevBuf<int> d_tile_ptr, d_tile_col;   // the sink-tiled CSR (n_tiles > 0)
     DevBuf<uint32_t> d_mask, d_fbits;
-    DevBuf<int> d_kind, d_orig, d_arr_off, d_arr_n, d_csr_ptr, d_csr_col, d_outdeg_f, d_fol, d_cbf;
+    DevBuf<int> d_kind, d_orig, d_arr_off, d_arr_n, d_csr_ptr, d_csr_col, d_outdeg_f, d_fol, d_cbf, d_gen_cls;
     DevBuf<uint32_t> d_seed;
     DevBuf<double> d_p0, d_p1, d_p2, d_arr_a, d_arr_b;
     int upload();
@@ -206,7 +206,8 @@ int rq_graph::upload()
         (rc = d_p0.upload(p0)) || (rc = d_p1.upload(p1)) ||
         (rc = d_p2.upload(p2)) || (rc = d_arr_a.upload(arr_a)) ||
         (rc = d_arr_b.upload(arr_b)) || (rc = d_sink_ids.upload(sink_ids)) ||
-        (rc = d_csr_col_el.upload(csr_col_el)) || (rc = d_cbf.upload(cbf)))
+        (rc = d_csr_col_el.upload(csr_col_el)) || (rc = d_cbf.upload(cbf)) ||
+        (rc = d_gen_cls.upload(gen_cls)))
         return rc;
     if (multi && ((rc = d_lay_ptr.upload(lay_ptr)) || (rc = d_lay_end.upload(lay_end))))
         return rc;
@@ -336,7 +337,7 @@ struct Chunk {
 };
 
 GenArgs gen_args(const rq_graph* g, const Plan& p, const rq_batch_desc* b, const rq_outputs* out,
-                 const Chunk& ch)
+                 const Chunk& ch, const Knobs& kn)
 {
     GenArgs ga{};
     ga.n_chunk = ch.C;
@@ -382,6 +383,10 @@ GenArgs gen_args(const rq_graph* g, const Plan& p, const rq_batch_desc* b, const
         ga.n_rd = b->n_rd;
         ga.rd_times = b->rd_times;
         ga.rd_off = b->rd_off;
+    }
+    if (kn.gen_split) {
+        ga.cls = g->d_gen_cls.p;
+        for (int c = 0; c < 3; ++c) ga.cls_n[c] = g->gen_n[c];
     }
     return ga;
 }
@@ -713,7 +718,7 @@ int rq_run_batch(rq_graph_t g, const rq_batch_desc* b, const rq_outputs* out, vo
         const Chunk ch{c0, std::min(p.chunk, p.R - c0), ws,
                        ws + p.off_set0 + (size_t)(ci % p.nbuf) * p.set_stride};
         // gen (the generating fused sweep makes its arrivals itself)
-        const GenArgs ga = gen_args(g, p, b, out, ch);
+        const GenArgs ga = gen_args(g, p, b, out, ch, kn);
         if (!p.fw || p.fwm) {
             TimedLaunch tl(K_GEN, s);
             if (rq_launch_gen(ga, s) != hipSuccess) return RQ_EHIP;

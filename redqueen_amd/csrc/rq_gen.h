@@ -1,7 +1,7 @@
 // rq_gen.h -- one source's arrival stream as a step machine (one lane, one source).
 //
-// Shared by rq_gen_streams (streams written to HBM) and the fused sweep (rings
-// refilled in LDS), so both produce the same bits.  One step() = one candidate:
+// Shared by the generator kernels (rq_gen.hip: streams written to HBM) and the fused sweep
+// (rings refilled in LDS), so both produce the same bits.  One step() = one candidate:
 //   Poisson / Poisson2  opt_model.py:424-433 / :396-405 -- exponential gaps
 //                       t += Exp(1) / rate (one draw per arrival)
 //   Hawkes              opt_model.py:466-490 -- Ogata thinning with the exponential
@@ -25,7 +25,31 @@
 
 namespace rq {
 
-struct SrcGen {
+// the Philox key's seed of stream j in replica i (global id)
+__device__ __forceinline__ uint32_t gen_seed(const GenArgs& a, int j, int64_t i, bool is_ctrl)
+{
+    const int64_t k = a.seed_mod > 0 ? i % a.seed_mod : i;
+    if (is_ctrl) return a.ctrl_seed ? a.ctrl_seed[i] : a.ctrl_seed0 + (uint32_t)k;
+    if (a.randomize) {
+        const uint32_t u = a.world_seed ? a.world_seed[i] : a.world_seed0 + (uint32_t)k;
+        return u + 99u * (uint32_t)a.orig_idx[j];   // randomize_other_sources, opt_model.py:795-804
+    }
+    return a.seed[j];
+}
+
+// rq_std_exponential of a 53-bit uniform: 1 - u is a normal number in [2^-53, 1], so rq_log's
+// special cases cannot occur and its body is called directly, as straight-line code
+__device__ __forceinline__ double gen_exponential(uint32_t w0, uint32_t w1)
+{
+    return -rq_log_normal(rq_dbl_bits(1.0 - rq_uniform53(w0, w1)), 0, 1);
+}
+
+// KIND < 0: the source kind is data (`kind`).  KIND = RQ_SRC_*: the caller knows that every
+// stream it generates is of that kind, so the tests on it fold at compile time and the other
+// kinds' state leaves the register allocation (rq_gen_hawkes); the arithmetic is this one
+// definition either way.
+template <int KIND = -1>
+struct SrcGenT {
     uint32_t k0, k1;        // Philox key (seed, kind salt)
     uint32_t d;             // next draw index (< 2^32 draws per source)
     // the draws are turned into exponentials ahead of their use, so the Philox rounds and
@@ -45,6 +69,8 @@ struct SrcGen {
     const double* tb;       // PWConst rates
     int na, ri;
 
+    __device__ __forceinline__ bool is(int k) const { return KIND < 0 ? kind == k : KIND == k; }
+
     __device__ __forceinline__ void none()
     {
         etab = nullptr;
@@ -59,7 +85,7 @@ struct SrcGen {
     {
         uint32_t c[4] = {call, 0u, 0u, 0u};
         philox4x32_10(c, k0, k1);
-        e = rq_std_exponential(rq_uniform53(c[0], c[1]));
+        e = KIND < 0 ? rq_std_exponential(rq_uniform53(c[0], c[1])) : gen_exponential(c[0], c[1]);
         u = rq_uniform53(c[2], c[3]);
     }
 
@@ -68,17 +94,7 @@ struct SrcGen {
         etab = etab_;
         const bool is_ctrl = j == a.ctrl_idx;
         kind = is_ctrl ? a.ctrl_stream_kind : a.kind[j];
-        const int64_t k = a.seed_mod > 0 ? i % a.seed_mod : i;
-        uint32_t seed;
-        if (is_ctrl) {
-            seed = a.ctrl_seed ? a.ctrl_seed[i] : a.ctrl_seed0 + (uint32_t)k;
-        } else if (a.randomize) {
-            const uint32_t u = a.world_seed ? a.world_seed[i] : a.world_seed0 + (uint32_t)k;
-            seed = u + 99u * (uint32_t)a.orig_idx[j];   // randomize_other_sources, opt_model.py:795-804
-        } else {
-            seed = a.seed[j];
-        }
-        k0 = seed;
+        k0 = gen_seed(a, j, i, is_ctrl);
         k1 = kind_salt(kind, is_ctrl);
         d = 0u;
         en = e1n = u2n = 0.0;
@@ -91,18 +107,18 @@ struct SrcGen {
         p0 = p1 = nbeta = 0.0;
         ta = tb = nullptr;
         na = ri = 0;
-        if (kind == RQ_SRC_POISSON || kind == RQ_SRC_POISSON2) {
+        if (is(RQ_SRC_POISSON) || is(RQ_SRC_POISSON2)) {
             const double rate = is_ctrl ? a.ctrl_rate[i] : a.p0[j];
             if (rate > 0.0) inv = 1.0 / rate;
             else done = true;
-        } else if (kind == RQ_SRC_HAWKES) {
+        } else if (is(RQ_SRC_HAWKES)) {
             p0 = a.p0[j];
             p1 = a.p1[j];
             nbeta = -a.p2[j];
             B = p0;   // lambda at start (no excitation yet)
             if (B > 0.0) inv = 1.0 / B;
             else done = true;
-        } else if (kind == RQ_SRC_PWCONST) {
+        } else if (is(RQ_SRC_PWCONST)) {
             na = a.arr_n[j];
             ta = a.arr_a + a.arr_off[j];
             tb = a.arr_b + a.arr_off[j];
@@ -111,7 +127,7 @@ struct SrcGen {
             if (mx > 0.0) inv = 1.0 / mx;
             else done = true;
             p0 = mx;
-        } else if (kind == RQ_SRC_REALDATA) {
+        } else if (is(RQ_SRC_REALDATA)) {
             const int rk = (a.rd_k && !is_ctrl) ? a.rd_k[j] : -1;
             if (rk >= 0) {   // this replica's own times (a registered static broadcaster)
                 const int64_t o = a.rd_off[i * a.n_rd + rk];
@@ -125,20 +141,20 @@ struct SrcGen {
         } else {
             done = true;   // the controlled slot of an Opt / wall-only run: no stream
         }
-        if (!done && (kind == RQ_SRC_HAWKES || kind == RQ_SRC_PWCONST)) draw2(0u, e1n, u2n);
+        if (!done && (is(RQ_SRC_HAWKES) || is(RQ_SRC_PWCONST))) draw2(0u, e1n, u2n);
     }
 
     // one candidate; true (and *out) when it is an arrival.  Sets done past `end`.
     __device__ __forceinline__ bool step(double* out, double end)
     {
         if (done) return false;
-        if (kind == RQ_SRC_REALDATA) {
+        if (is(RQ_SRC_REALDATA)) {
             *out = ta[ri];
             ++ri;
             done = ri >= na;
             return true;
         }
-        const bool poisson = kind == RQ_SRC_POISSON || kind == RQ_SRC_POISSON2;
+        const bool poisson = is(RQ_SRC_POISSON) || is(RQ_SRC_POISSON2);
         double e, u2 = 0.0;
         if (poisson) {
             if ((d & 1u) == 0u) {
@@ -167,7 +183,7 @@ struct SrcGen {
             *out = tc;
             return true;
         }
-        if (kind == RQ_SRC_HAWKES) {
+        if (is(RQ_SRC_HAWKES)) {
             const double decay = rq_exp_t(nbeta * (tc - tau), etab);
             const double rate = p0 + eta * decay;
             const bool acc = u2 * B < rate;   // u2 < rate / B without the f64 division
@@ -203,5 +219,6 @@ struct SrcGen {
         return false;
     }
 };
+using SrcGen = SrcGenT<>;
 
 }  // namespace rq

@@ -133,6 +133,9 @@ struct Knobs {
     bool ctrl_draws = true;
     // RQ_SWEEP_SCAN=0: the scan kernel instead of the sweep's own scan; A/B, test_gpu_sweep_scan
     bool sweep_scan = true;
+    // RQ_GEN_SPLIT=0: rq_gen_streams for every stream instead of rq_gen_classes' body per
+    // class of source kinds; A/B, test_gpu_gen_split
+    bool gen_split = true;
     // RQ_PHASEC_BLK=0: the merged sink-bit sweep keeps one event per lane in phase C (the word
     // loop); A/B, test_gpu_phase_c_blocked
     bool phasec_blk = true;
@@ -217,6 +220,10 @@ struct GraphTopo {
     // or has a larger src_id (opt_model.py:279-281, :289-290): the sweeps' per-stream flag,
     // in global memory for the GT instances (the others build it in LDS)
     std::vector<int> cbf;
+    // the streams but the controlled slot by generator class -- gen_n[0] Hawkes, gen_n[1]
+    // Poisson / Poisson2, gen_n[2] others -- for rq_gen_classes' body per class
+    std::vector<int> gen_cls;
+    int gen_n[3] = {0, 0, 0};
     // the CSR cut into sink tiles of RQ_FOLLOWERS_TILE_SINKS columns (tile i owns columns
     // [i TS, min((i + 1) TS, n_sinks))), for graphs without duplicate edges and with at most
     // RQ_FOLLOWERS_TILED_MAX_SINKS sinks (n_tiles == 0 otherwise): tile_ptr[n_tiles][n_str + 1]

@@ -49,6 +49,11 @@ struct GenArgs {
     int n_rd;
     const double* rd_times;
     const int64_t* rd_off;
+    // rq_launch_gen only: the graph's streams by generator class (GraphTopo.gen_cls: H, P, G;
+    // the controlled slot is not in it), cls_n streams each.  Null (RQ_GEN_SPLIT=0):
+    // rq_gen_streams for every stream.
+    const int* cls;
+    int cls_n[3];
 };
 
 // global id of a call's local replica: the replica list (rq_batch_desc.rep_idx) or the

@@ -11,10 +11,11 @@
 //   sall     i32  [C]                  sink columns S_all seen by the replica
 //
 // Kernel roles (reference file:line they replace):
-//   rq_gen_streams  Poisson :424-433, Poisson2 :396-405, Hawkes :466-490,
-//                   PiecewiseConst :642-663, RealData :722-750 -- one lane per
-//                   (replica, source), 256 replicas of ONE source per block so a
-//                   block never diverges on the source kind.
+//   rq_gen_classes  (rq_gen.hip) Poisson :424-433, Poisson2 :396-405, Hawkes
+//                   :466-490, PiecewiseConst :642-663, RealData :722-750 -- one lane
+//                   per (replica, source), 256 replicas of ONE source per block so a
+//                   block never diverges on the source kind and runs the body of
+//                   its kind's class.
 //   rq_sweep        Manager.run_dynamic :241-314 + Opt.get_next_interval
 //                   :502-544 + State.apply_event :61-83 + the per-row part of
 //                   rank_of_src_in_df utils.py:38-56 -- one wavefront per
@@ -41,91 +42,7 @@ using namespace rq;
 // ============================================================================
 // 1. arrival streams
 // ============================================================================
-__global__ __launch_bounds__(256) void rq_gen_streams(GenArgs a)
-{
-    // rq_exp's table in LDS: a Hawkes candidate's exp looks up two per-lane words in its
-    // dependent chain (from __constant__ memory these were vector loads at L1/L2 latency)
-    __shared__ uint64_t etab[RQ_EXP_TAB_N];
-    for (int e = threadIdx.x; e < RQ_EXP_TAB_N; e += blockDim.x) etab[e] = rq_exp_tab_c[e];
-    __syncthreads();
-    const int64_t rl = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int j = (int)(blockIdx.z * gridDim.y + blockIdx.y);   // > 32768 streams fold into z
-    if (rl >= a.n_chunk || j >= a.n_str) return;
-    const int64_t o = a.chunk0 + rl;      // local output index
-    const int64_t i = rq_replica_of(a, o);   // global id (seeds)
-    SrcGen gen;
-    gen.init(a, j, i, etab);
-
-    double* out = a.streams + rl * a.capsum + a.st_off[j];   // 128-byte aligned (host pads)
-    const int cap = a.cap[j];                                   // multiple of 16
-    int n = 0;
-    bool ovf = false;
-    // arrivals are staged RQ_GEN_W at a time in registers (compile-time shift, no
-    // scratch) and written as one lane-contiguous chunk: 16 = a whole 128-byte line per
-    // lane, so no line is written in halves at different times (C3: written bytes 1.22 ->
-    // 1.04 x the 8 B per arrival; 8: gen 5 % faster at 90 instead of 106 VGPRs)
-#ifndef RQ_GEN_W
-#define RQ_GEN_W 16
-#endif
-    constexpr int GW = RQ_GEN_W;
-    static_assert(GW == 8 || GW == 16, "staging width");
-    double sb[GW];
-#pragma unroll
-    for (int k = 0; k < GW; ++k) sb[k] = 0.0;
-    while (!gen.done && !ovf) {
-        double tv;
-        if (gen.step(&tv, a.end)) {
-            if (n < cap) {
-#pragma unroll
-                for (int k = 0; k + 1 < GW; ++k) sb[k] = sb[k + 1];
-                sb[GW - 1] = tv;
-                ++n;
-                if ((n & (GW - 1)) == 0) {
-                    double4* d = reinterpret_cast<double4*>(out + n - GW);
-#pragma unroll
-                    for (int k = 0; k < GW / 4; ++k) d[k] = make_double4(sb[4 * k], sb[4 * k + 1], sb[4 * k + 2], sb[4 * k + 3]);
-                }
-            } else {
-                ovf = true;
-            }
-        }
-    }
-    {   // the last partial chunk: values sit in sb[GW-r .. GW-1]; written as one whole
-        // chunk (slots past n hold stale values nobody reads: readers stop at slen)
-        const int r = n & (GW - 1);
-        if (r > 0) {
-            // shift the staged values left by GW - r (log-steps of static shifts: no scratch).
-            // RQ_GEN_TAIL_STEPS: each step selects between two VALUES per slot, GW x log2 GW
-            // two-way selects in all.  0 (A/B): the select between two array elements, an
-            // lvalue the compiler turns into one element at a selected index -- a GW-way
-            // compare-and-select chain per output word and step
-#ifndef RQ_GEN_TAIL_STEPS
-#define RQ_GEN_TAIL_STEPS 1
-#endif
-            const int sh = GW - r;
-#pragma unroll
-            for (int st = 1; st < GW; st <<= 1) {
-                const bool on = (sh & st) != 0;
-#pragma unroll
-                for (int k = 0; k < GW; ++k) {
-#if RQ_GEN_TAIL_STEPS
-                    const double up = sb[k + st < GW ? k + st : GW - 1], keep = sb[k];
-                    sb[k] = on ? up : keep;
-#else
-                    sb[k] = on ? sb[k + st < GW ? k + st : GW - 1] : sb[k];
-#endif
-                }
-            }
-            // whole 64-byte halves, only those holding arrivals
-            double4* d = reinterpret_cast<double4*>(out + (n - r));
-#pragma unroll
-            for (int k = 0; k < GW / 4; ++k)
-                if (k < 2 || r > 8) d[k] = make_double4(sb[4 * k], sb[4 * k + 1], sb[4 * k + 2], sb[4 * k + 3]);
-        }
-    }
-    a.slen[(int64_t)j * a.slen_stride + rl] = n;   // consecutive lanes, consecutive ints
-    if (ovf) atomicOr(&a.status[o], RQ_ST_STREAM_OVERFLOW);
-}
+// rq_gen.hip: rq_gen_classes, rq_gen_streams and rq_launch_gen
 
 // ============================================================================
 // 2. sweep: one wavefront per replica, 64-arrival tiles in three phases.
@@ -1215,15 +1132,6 @@ static hipError_t launch_sweep_t(SweepKernel k, bool gs, const SweepArgs& a, hip
         if (cap < blocks) blocks = cap;
     }
     hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * a.wpb), a.lds_total, s, a);
-    return hipGetLastError();
-}
-
-hipError_t rq_launch_gen(const GenArgs& a, hipStream_t s)
-{
-    if (a.n_chunk <= 0 || a.n_str <= 0) return hipSuccess;
-    const unsigned gy = (unsigned)std::min(a.n_str, 32768);
-    dim3 grid((unsigned)((a.n_chunk + 255) / 256), gy, (unsigned)((a.n_str + gy - 1) / gy));
-    hipLaunchKernelGGL(rq_gen_streams, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

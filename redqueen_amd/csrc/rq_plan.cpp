@@ -24,6 +24,7 @@ Knobs read_knobs()
     if (const char* e = getenv("RQ_FWM")) k.fwm = atoi(e) != 0;
     if (const char* e = getenv("RQ_CTRL_DRAWS")) k.ctrl_draws = atoi(e) != 0;
     if (const char* e = getenv("RQ_SWEEP_SCAN")) k.sweep_scan = atoi(e) != 0;
+    if (const char* e = getenv("RQ_GEN_SPLIT")) k.gen_split = atoi(e) != 0;
     if (const char* e = getenv("RQ_PHASEC_BLK")) k.phasec_blk = atoi(e) != 0;
     if (const char* e = getenv("RQ_FW_W")) k.fw_w = atoi(e);
     if (const char* e = getenv("RQ_PIPE")) k.pipe = std::max(1, std::min(3, atoi(e)));

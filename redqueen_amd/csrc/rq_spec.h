@@ -59,8 +59,14 @@ RQ_HD double rq_uniform53(uint32_t a, uint32_t b)
     return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) / 9007199254740992.0;
 }
 
-/* Natural log for finite x > 0 (subnormals handled; x <= 0 -> -inf/NaN). */
-RQ_HD double rq_log(double x)
+/* rq_log's body for a normal finite x > 0 with bits ux (a scaled subnormal: k = -54).  A
+ * caller that knows its argument is one (1 - u of a 53-bit uniform lies in [2^-53, 1]) calls
+ * this directly and so has no special-case branch in front of it.  straight (a constant):
+ * no early return for x = 2^k, so the body is one basic block and several logarithms can be
+ * scheduled together.  The general formula gives that case the same bits: f = +0 makes s, z,
+ * w, R and hfsq +0, the bracket is (+0 - dk ln2_lo) - 0 = -(dk ln2_lo), and a - (-b) is
+ * a + b in IEEE arithmetic (dk = 0: +0 - +0 = +0 = +0 + +0). */
+RQ_HD double rq_log_normal(uint64_t ux, int32_t k, int straight)
 {
     const double ln2_hi = 6.93147180369123816490e-01;
     const double ln2_lo = 1.90821492927058770002e-10;
@@ -72,19 +78,6 @@ RQ_HD double rq_log(double x)
     const double Lg6 = 1.531383769920937332e-01;
     const double Lg7 = 1.479819860511658591e-01;
 
-    uint64_t ux = rq_dbl_bits(x);
-    if (!(x > 0.0)) {
-        if (x == 0.0) return rq_bits_dbl(0xfff0000000000000ull);  /* -inf */
-        return rq_bits_dbl(0x7ff8000000000000ull);  /* NaN */
-    }
-    if ((ux >> 52) >= 0x7ffu) return x + x;      /* +inf / NaN */
-
-    int32_t k = 0;
-    if ((ux >> 52) == 0) {                       /* subnormal: scale by 2^54 */
-        x = x * 18014398509481984.0;
-        ux = rq_dbl_bits(x);
-        k = -54;
-    }
     int32_t hx = (int32_t)(ux >> 32);
     k += (hx >> 20) - 1023;
     hx &= 0x000fffff;
@@ -102,8 +95,27 @@ RQ_HD double rq_log(double x)
     double t2 = z * (Lg1 + w * (Lg3 + w * (Lg5 + w * Lg7)));
     double R = t2 + t1;
     double hfsq = 0.5 * f * f;
-    if (f == 0.0) return dk * ln2_hi + dk * ln2_lo;
+    if (!straight && f == 0.0) return dk * ln2_hi + dk * ln2_lo;
     return dk * ln2_hi - ((hfsq - (s * (hfsq + R) + dk * ln2_lo)) - f);
+}
+
+/* Natural log for finite x > 0 (subnormals handled; x <= 0 -> -inf/NaN). */
+RQ_HD double rq_log(double x)
+{
+    uint64_t ux = rq_dbl_bits(x);
+    if (!(x > 0.0)) {
+        if (x == 0.0) return rq_bits_dbl(0xfff0000000000000ull);  /* -inf */
+        return rq_bits_dbl(0x7ff8000000000000ull);  /* NaN */
+    }
+    if ((ux >> 52) >= 0x7ffu) return x + x;      /* +inf / NaN */
+
+    int32_t k = 0;
+    if ((ux >> 52) == 0) {                       /* subnormal: scale by 2^54 */
+        x = x * 18014398509481984.0;
+        ux = rq_dbl_bits(x);
+        k = -54;
+    }
+    return rq_log_normal(ux, k, 0);
 }
 
 /* e^x, table-driven (no division): x = k ln2/32 + r with k = round(32 x / ln2) from the

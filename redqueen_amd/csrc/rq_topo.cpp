@@ -213,6 +213,21 @@ int topo_build(const rq_graph_desc* d, GraphTopo* g)
     g->cbf.resize(g->n_str);
     for (int j = 0; j < g->n_str; ++j) g->cbf[j] = g->is_static[j] || g->ctrl_src_id < g->src_id[j];
 
+    // the generator's class lists: Hawkes, then the Poisson kinds, then the rest, each in
+    // stream order; the controlled slot joins its call's class at the launch
+    g->gen_cls.clear();
+    for (int c = 0; c < 3; ++c) {
+        g->gen_n[c] = 0;
+        for (int j = 0; j < g->n_str; ++j) {
+            if (j == g->ctrl_idx) continue;
+            const int k = g->kind[j];
+            const int cj = k == RQ_SRC_HAWKES ? 0 : (k == RQ_SRC_POISSON || k == RQ_SRC_POISSON2) ? 1 : 2;
+            if (cj != c) continue;
+            g->gen_cls.push_back(j);
+            ++g->gen_n[c];
+        }
+    }
+
     // the sink-tiled CSR (rq_host.h): a stable counting sort of the edges by (tile, stream)
     if (!g->multi && g->n_sinks <= RQ_FOLLOWERS_TILED_MAX_SINKS) {
         const int TS = RQ_FOLLOWERS_TILE_SINKS;
