@@ -28,6 +28,12 @@
 //       row of integral cells sums exactly in any order, which is what numpy's
 //       pairwise row sum returns.  A dataframe with two rows of one sink at one t
 //       (a pandas pivot MEAN, possibly fractional) is handed to rq_rp_seq.
+//       The batch algorithm stands once, in rp_fast_body<NK, TIER, R>: rq_rp_fast_s
+//       (small LDS table), rq_rp_fast (full LDS table, global table) and rq_rc_apply
+//       (the chunked replay below: one chunk of a long dataframe per workgroup) are its
+//       instances, and RpLds is the one description of its dynamic LDS, for the kernel
+//       and for the launch code.
+//   rq_rc_*          the chunked replay: ONE dataframe over many workgroups (see there).
 //   rq_rp_keys       sorted unique sink ids of those dataframes (bitonic sort).
 //   rq_rp_seq<NK>    the exact sequential replay (one wavefront per dataframe,
 //       pivot-cell means and numpy-pairwise row sums while fractional cells are
@@ -142,13 +148,6 @@ __device__ __forceinline__ int rp_gbits(int64_t n)
 // and these chains are the batch's critical path) ----
 // inclusive 64-lane sum of 32-bit values (two's complement wrap, so int works too)
 __device__ __forceinline__ int scan_add_i32(int v) { return (int)wave_scan_add((uint32_t)v); }
-// inclusive 64-lane sum of int32 values as int64 (16-bit halves scanned apart: exact)
-__device__ __forceinline__ int64_t scan_add_i64_of_i32(int v)
-{
-    const int hi = scan_add_i32(v >> 16);
-    const int lo = scan_add_i32(v & 0xFFFF);
-    return (int64_t)hi * 65536 + (int64_t)lo;
-}
 // inclusive 64-lane sum of int64 values of magnitude < 2^47 (16-bit low halves and
 // the high parts scanned apart: exact)
 __device__ __forceinline__ int64_t scan_add_i64_small(int64_t v)
@@ -204,6 +203,74 @@ struct RpAcc {
     int c[NK];      // cells <= K-1
 };
 
+// ---- the chunked replay's chunk of a workgroup and its dataframe's sink table
+// (built by rq_rc_hash / rq_rc_dense below) ----
+__device__ __forceinline__ int64_t rc_df_of_chunk(const RpArgs& a, int64_t c)
+{
+    int64_t lo = 0, hi = a.n_df;   // the last d with cbase[d] <= c (empty dfs share a base)
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (a.cbase[mid] <= c) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+constexpr int RC_HBITS = 13;   // log2(RC_HT)
+static_assert((1 << RC_HBITS) == RC_HT, "RC_HT");
+static_assert(RC_L % RP_B == 0, "chunks hold whole batches");
+constexpr int RC_SKIP = RP_BADOFF | RP_EMPTYDF | RP_CSKIP;
+
+__device__ __forceinline__ int rc_dense(const uint64_t* hk, const int* hd, uint64_t k)
+{
+    uint32_t h = rp_hash(k, RC_HBITS);
+    for (int p = 0; p < RC_HT; ++p) {   // rq_rc_hash inserted every key (bounded all the same)
+        if (hk[h] == k) return hd[h];
+        h = (h + 1) & (RC_HT - 1);
+    }
+    return 0;
+}
+
+// the chunk of this block: df d, rows [c0, c1); false if the block has none
+__device__ __forceinline__ bool rc_chunk(const RpArgs& a, int64_t& d, int64_t& r0, int64_t& r1, int64_t& c0,
+                                         int64_t& c1)
+{
+    const int64_t c = blockIdx.x;
+    if (c >= a.cbase[a.n_df]) return false;
+    d = rc_df_of_chunk(a, c);
+    r0 = df_begin(a, d);
+    r1 = df_end(a, d);
+    c0 = r0 + (c - a.cbase[d]) * RC_L;
+    c1 = c0 + RC_L < r1 ? c0 + RC_L : r1;
+    return true;
+}
+
+// ---- the batch body's dynamic LDS: byte offsets in carve order, every area rounded up
+// to 16 bytes.  The kernel carves by it and the launch code asks it for the size. ----
+constexpr int RP_TIER_CHUNK = 3;   // rp_fast_body's TIER of rq_rc_apply
+struct RpLds {
+    size_t tb = 0, eb = 0, gb = 0, lst = 0, wsum = 0, ws32 = 0, misc = 0, tkeys = 0, tst = 0, bytes = 0;
+    constexpr RpLds(int tier, int nK, int R)
+    {
+        const bool chunk = tier == RP_TIER_CHUNK;
+        const size_t br = (size_t)R * RP_B;
+        // the LDS table's slots + the sentinel id's; none: the global table, a chunk (no keys)
+        const size_t h = tier == 0 ? RP_HS + 1 : tier == 1 ? RP_H + 1 : 0;
+        auto take = [this](size_t b) {
+            const size_t at = bytes;
+            bytes += (b + 15) & ~(size_t)15;
+            return at;
+        };
+        tb = take(8 * (br + 2));                 // t: [0] prev, [1 + i], [br + 1] next
+        eb = take(chunk ? 0 : 8 * (br + 1));     // event ids: [0] prev, [1 + i]
+        gb = take(4 * br);                       // t-group of row i
+        lst = take(4 * br);                      // sink buckets: 2 row + own
+        wsum = take(8 * 16);                     // wave totals (int64)
+        ws32 = take((size_t)4 * 16 * (nK + 6));  // wave totals (int)
+        misc = take(4 * 16);                     // flags, counters
+        tkeys = take(8 * h);                     // the table's sink ids
+        tst = take(sizeof(RpSlot) * (chunk ? (size_t)RC_S : h));   // per-sink state
+    }
+};
+
 }  // namespace
 
 // ============================================================================
@@ -213,23 +280,44 @@ struct RpAcc {
 // RP_MID), 2: global table (those tier 1 gave up: RP_GLOBAL).  A batch is R * RP_B rows:
 // thread tid owns rows tid * R .. tid * R + R - 1 (row order within the thread, so every
 // block scan runs over per-thread partial sums: one barrier set per R * RP_B rows).
+// TIER 3 (RP_TIER_CHUNK, R == 1) is rq_rc_apply: the workgroup plays one chunk [lo, hi)
+// of its dataframe's rows [r0, r1) from the states rq_rc_scan left.  What the chunk owns:
+// its rows' range, the slot of a sink (an rc_dense lookup), the entering state and the
+// epilogue; rq_rc_sum already ran the fast path's checks and event counts.
 template <int NK, int TIER, int R>
 __device__ __forceinline__ void rp_fast_body(RpArgs a)
 {
     constexpr bool GLOBAL = TIER == 2;
+    constexpr bool CHUNK = TIER == RP_TIER_CHUNK;
+    static_assert(!CHUNK || R == 1, "chunks play one row per thread");
     constexpr int BR = R * RP_B;
-    const int64_t d = blockIdx.x;
+    constexpr RpLds L(TIER, NK, R);
     const int tid = threadIdx.x;
     const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // the dataframe's rows [r0, r1), of which this workgroup plays [lo, hi)
+    int64_t d, r0, r1, lo, hi;
+    if constexpr (CHUNK) {
+        if (!rc_chunk(a, d, r0, r1, lo, hi)) return;
+    } else {
+        d = blockIdx.x;
+    }
     RpInfo* inf = a.info + d;
-    if (GLOBAL && !(inf->flags & RP_GLOBAL)) return;   // only the dataframes the LDS pass gave up
-    if (TIER == 1 && a.first_tier == 0 && !(inf->flags & RP_MID)) return;   // ... the small pass gave up
-    if (TIER == a.first_tier && a.chunked && !(inf->flags & RP_CSKIP)) return;   // the chunked pass took it
-    const int64_t r0 = df_begin(a, d), r1 = df_end(a, d);
+    if constexpr (CHUNK) {
+        if (inf->flags & (RC_SKIP | RP_UNSORTED)) return;
+    } else {
+        if (GLOBAL && !(inf->flags & RP_GLOBAL)) return;   // only the dataframes the LDS pass gave up
+        if (TIER == 1 && a.first_tier == 0 && !(inf->flags & RP_MID)) return;   // ... the small pass gave up
+        if (TIER == a.first_tier && a.chunked && !(inf->flags & RP_CSKIP)) return;   // the chunked pass took it
+        r0 = df_begin(a, d);
+        r1 = df_end(a, d);
+        lo = r0;
+        hi = r1;
+    }
     const int64_t nd = r1 - r0;
     // a malformed caller range (decreasing / negative offsets, past n_rows, >= 2^31 rows:
     // the row positions below are int) touches no workspace; rq_rp_scan reports RQ_EINVAL
-    if (r0 < 0 || r1 < r0 || r1 > a.n_rows || nd >= ((int64_t)1 << 31)) {
+    // (rq_rc_plan flagged such a dataframe RC_SKIP)
+    if (!CHUNK && (r0 < 0 || r1 < r0 || r1 > a.n_rows || nd >= ((int64_t)1 << 31))) {
         if (TIER == a.first_tier && tid == 0) {
             inf->flags = RP_BADOFF;
             inf->n_piv = 0;
@@ -241,60 +329,75 @@ __device__ __forceinline__ void rp_fast_body(RpArgs a)
     }
 
     extern __shared__ __align__(16) unsigned char rp_smem[];
+    // the areas of L, each pointer stepped from the one before it: with every area at a
+    // constant offset from rp_smem instead, the two-row instances spill an SGPR
     unsigned char* sp = rp_smem;
-    auto carve = [&](size_t bytes) {
-        unsigned char* p = sp;
-        sp += (bytes + 15) & ~(size_t)15;
-        return p;
+    size_t sp_at = 0;
+    auto area = [&](size_t at) {
+        sp += at - sp_at;
+        sp_at = at;
+        return sp;
     };
-    double* tb = reinterpret_cast<double*>(carve(8 * (BR + 2)));         // [0] prev, [1+i], [BR+1] next
-    int64_t* eb = reinterpret_cast<int64_t*>(carve(8 * (BR + 1)));       // [0] prev eid, [1+i]
-    int* gb = reinterpret_cast<int*>(carve(4 * BR));                      // t-group of row i
-    int* lst = reinterpret_cast<int*>(carve(4 * BR));                     // sink buckets: 2 row + own
-    int64_t* wsum = reinterpret_cast<int64_t*>(carve(8 * 16));            // wave totals (int64)
-    int* ws32 = reinterpret_cast<int*>(carve(4 * 16 * (NK + 6)));         // wave totals (int)
-    int* misc = reinterpret_cast<int*>(carve(4 * 16));                    // flags, counters
+    double* tb = reinterpret_cast<double*>(area(L.tb));
+    int64_t* eb = reinterpret_cast<int64_t*>(area(L.eb));   // (a chunk has none)
+    int* gb = reinterpret_cast<int*>(area(L.gb));
+    int* lst = reinterpret_cast<int*>(area(L.lst));
+    int64_t* wsum = reinterpret_cast<int64_t*>(area(L.wsum));
+    int* ws32 = reinterpret_cast<int*>(area(L.ws32));
+    int* misc = reinterpret_cast<int*>(area(L.misc));
+    // the sink table: keys and capacity (the fast path inserts), or the chunked
+    // dataframe's table with its dense ids (looked up: a chunk's state has no keys)
     unsigned long long* tkeys;
     RpSlot* tst;
-    uint32_t tmask;
     int tbits;
     int64_t tcap;
-    if constexpr (GLOBAL) {
+    const uint64_t* hk = nullptr;
+    const int* hd = nullptr;
+    if constexpr (CHUNK) {
+        tkeys = nullptr;   // (a chunk inserts nothing: no keys, no capacity)
+        tbits = 0;
+        tcap = 0;
+        hk = a.ht_keys + d * RC_HT;
+        hd = a.ht_dense + d * RC_HT;
+        tst = reinterpret_cast<RpSlot*>(area(L.tst));
+    } else if constexpr (GLOBAL) {
         tbits = rp_gbits(nd);
         tcap = (int64_t)1 << tbits;
         tkeys = reinterpret_cast<unsigned long long*>(a.gkeys) + 4 * r0;
         tst = reinterpret_cast<RpSlot*>(a.gstate) + 4 * r0;
     } else {
-        constexpr int H = TIER == 0 ? RP_HS : RP_H;
         tbits = TIER == 0 ? RP_LOG_HS : RP_LOG_H;
-        tcap = H;
-        tkeys = reinterpret_cast<unsigned long long*>(carve(8 * (H + 1)));
-        tst = reinterpret_cast<RpSlot*>(carve(sizeof(RpSlot) * (H + 1)));
+        tcap = TIER == 0 ? RP_HS : RP_H;
+        tkeys = reinterpret_cast<unsigned long long*>(area(L.tkeys));
+        tst = reinterpret_cast<RpSlot*>(area(L.tst));
     }
-    tmask = (uint32_t)(tcap - 1);
+    const uint32_t tmask = (uint32_t)(tcap - 1);
     // misc: [0] unique sinks, [1] sentinel-key seen, [2] dup, [3] unsorted, [4] eid bad,
     //       [5] own events, [6] world events, [7] key dump cursor, [8] bucket allocator,
     //       [9] table full (a batch's new sinks found no empty slot: this tier gives up)
+    //       (a chunk: [2] and [8] only)
     if (tid < 16) misc[tid] = 0;
-    if (TIER == a.first_tier && tid == 0) {   // this call's status (the first pass)
-        inf->flags = 0;
-        // a dataframe every tier gives up (RQ_EOVERFLOW) reports these as they stand: the
-        // host never clears the workspace
-        inf->n_piv = 0;
-        inf->n_own = 0;
-        inf->n_world = 0;
-        inf->S = 0;
+    if constexpr (!CHUNK) {
+        if (TIER == a.first_tier && tid == 0) {   // this call's status (the first pass)
+            inf->flags = 0;
+            // a dataframe every tier gives up (RQ_EOVERFLOW) reports these as they stand: the
+            // host never clears the workspace
+            inf->n_piv = 0;
+            inf->n_own = 0;
+            inf->n_world = 0;
+            inf->S = 0;
+        }
+        for (int64_t h = tid; h <= tcap; h += RP_B) {
+            tkeys[h] = RP_EMPTY_KEY;
+            tst[h] = RpSlot{0, 0, -1, 0};
+        }
+        if (GLOBAL && 2 * nd > tcap) {   // > 2^23 unique sinks possible: not supported
+            if (tid == 0) atomicOr(&inf->flags, RP_BIG);
+            return;
+        }
+        if (GLOBAL) __threadfence();   // the table's reset reaches L2 before the atomics below
+        __syncthreads();
     }
-    for (int64_t h = tid; h <= tcap; h += RP_B) {
-        tkeys[h] = RP_EMPTY_KEY;
-        tst[h] = RpSlot{0, 0, -1, 0};
-    }
-    if (GLOBAL && 2 * nd > tcap) {   // > 2^23 unique sinks possible: not supported
-        if (tid == 0) atomicOr(&inf->flags, RP_BIG);
-        return;
-    }
-    if (GLOBAL) __threadfence();   // the table's reset reaches L2 before the atomics below
-    __syncthreads();
 
     // the bucket word of a sink: LDS atomics, or (global table) atomics at L2 for every
     // access -- the CU's L1 may hold a stale copy of a line an atomic changed
@@ -307,17 +410,21 @@ __device__ __forceinline__ void rp_fast_body(RpArgs a)
     int km1[NK];
 #pragma unroll
     for (int q = 0; q < NK; ++q) km1[q] = a.Ks[q] - 1;
-    const bool has_eid = a.eid != nullptr;
+    // (a chunk reads no event ids: has_eid folds to false and takes their code with it)
+    const bool has_eid = !CHUNK && a.eid != nullptr;
 
 #ifdef RQ_PHASE_CLOCK
-    // diagnostic builds: per-wave s_memtime per phase of the batch loop (RQ_CLK_REPLAY)
+    // diagnostic builds: per-wave s_memtime per phase of the batch loop (RQ_CLK_REPLAY);
+    // the fast instances only
     unsigned long long ck[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long tk = __builtin_amdgcn_s_memtime();
-#define RP_CLK(q)                                                   \
-    do {                                                            \
-        const unsigned long long t2 = __builtin_amdgcn_s_memtime(); \
-        ck[q] += t2 - tk;                                           \
-        tk = t2;                                                    \
+#define RP_CLK(q)                                                       \
+    do {                                                                \
+        if constexpr (!CHUNK) {                                         \
+            const unsigned long long t2 = __builtin_amdgcn_s_memtime(); \
+            ck[q] += t2 - tk;                                           \
+            tk = t2;                                                    \
+        }                                                               \
     } while (0)
 #else
 #define RP_CLK(q) \
@@ -332,6 +439,57 @@ __device__ __forceinline__ void rp_fast_body(RpArgs a)
 #pragma unroll
     for (int q = 0; q < NK; ++q) carry.c[q] = 0;
     bool aborted = false;
+    double t_enter = 0.0;   // t of the row before the first batch
+    if constexpr (CHUNK) {
+        // every sink's state entering the chunk (rq_rc_scan), and the pivot row they sum to
+        const int64_t c = blockIdx.x;
+        const int S = inf->S;
+        const RcState* stin = a.state + c * RC_S;
+        if (lo > r0) t_enter = a.t[lo - 1];
+        const bool spans = lo > r0 && a.t[lo] == t_enter;   // the chunk continues the previous t-group
+        Gc = a.gbase[c];
+        int64_t ps = 0;
+        int pv = 0, pc[NK];
+#pragma unroll
+        for (int q = 0; q < NK; ++q) pc[q] = 0;
+        for (int s = tid; s < S; s += RP_B) {
+            const RcState e = stin[s];
+            if (e.r >= 0) {
+                // cnt = r + 1, lastown = 1: the next row's rank is r + 1; a cell in the
+                // spanning t-group keeps its group (a second row there is a pivot mean)
+                tst[s] = RpSlot{e.r + 1, 1, (spans && e.last_t == t_enter) ? (int)(Gc - 1) : -1, 0};
+                ps += e.r;
+                pv += 1;
+#pragma unroll
+                for (int q = 0; q < NK; ++q) pc[q] += e.r <= km1[q] ? 1 : 0;
+            } else {
+                tst[s] = RpSlot{0, 0, -1, 0};
+            }
+        }
+        {
+            int64_t s64 = ps;   // this wave's sum (int64 butterfly)
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s64 += __shfl_xor(s64, o, 64);
+            const int sv = scan_add_i32(pv);
+            if (lane == 63) {
+                wsum[w] = s64;
+                ws32[80 + w] = sv;
+            }
+#pragma unroll
+            for (int q = 0; q < NK; ++q) {
+                const int sq = scan_add_i32(pc[q]);
+                if (lane == 63) ws32[96 + 16 * q + w] = sq;
+            }
+        }
+        __syncthreads();
+        int64_t pre64;
+        int pre;
+        totals_add(wsum, w, pre64, carry.s);
+        totals_add(ws32 + 80, w, pre, carry.v);
+#pragma unroll
+        for (int q = 0; q < NK; ++q) totals_add(ws32 + 96 + 16 * q, w, pre, carry.c[q]);
+        __syncthreads();   // totals read before the batch loop reuses them
+    }
 
     // A batch's rows reach the workgroup through LDS: the loads for batch b + 1 are
     // issued at the top of batch b and consumed only at its end (prep), so they are
@@ -343,13 +501,13 @@ __device__ __forceinline__ void rp_fast_body(RpArgs a)
     uint32_t slot_c[R];  // ... their sinks' slots
     auto load = [&](int64_t nb0, double (&t_)[R], int64_t (&s_)[R], int64_t (&k_)[R],
                     int64_t (&e_)[R]) __attribute__((always_inline)) {
-        // unconditional loads at a clamped row (prep masks the rows past r1): no
+        // unconditional loads at a clamped row (prep masks the rows past hi): no
         // exec-masked zeroing of the destinations, whose write-after-write wait on the
         // previous batch's loads stalled the loop top
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int64_t ii = nb0 + tid * R + r;
-            const int64_t ic = ii < r1 ? ii : r1 - 1;   // nd > 0 (the caller checks)
+            const int64_t ic = ii < hi ? ii : hi - 1;   // hi > lo (the caller checks)
             t_[r] = a.t[ic];
             s_[r] = a.src[ic];
             k_[r] = a.sink[ic];
@@ -361,18 +519,20 @@ __device__ __forceinline__ void rp_fast_body(RpArgs a)
                     int64_t e_before) __attribute__((always_inline)) {
         if (tid == 0) {
             tb[0] = t_before;
-            eb[0] = e_before;
+            if constexpr (!CHUNK) eb[0] = e_before;
             tb[BR + 1] = t_after;
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int row = tid * R + r;
-            const bool v = nb0 + row < r1;
+            const bool v = nb0 + row < hi;
             tb[1 + row] = v ? t_[r] : 0.0;
             if (has_eid) eb[1 + row] = e_[r];
             own_c[r] = v && s_[r] == a.src_id;
             slot_c[r] = 0;
-            if (v) {
+            if constexpr (CHUNK) {
+                if (v) slot_c[r] = (uint32_t)rc_dense(hk, hd, (uint64_t)k_[r]);
+            } else if (v) {
                 if ((uint64_t)k_[r] == RP_EMPTY_KEY) {
                     slot_c[r] = (uint32_t)tcap;   // the sentinel id's own slot
                     if (misc[1] == 0 && atomicExch(&misc[1], 1) == 0) atomicAdd(&misc[0], 1);
@@ -391,20 +551,21 @@ __device__ __forceinline__ void rp_fast_body(RpArgs a)
     if (nd > 0) {
         double t0[R];
         int64_t s0[R], k0[R], e0[R];
-        load(r0, t0, s0, k0, e0);
+        load(lo, t0, s0, k0, e0);
+        // (the t after a batch is the frame's: a chunk's last t-group may go on in the next)
         double ta = 0.0;
-        if (tid == 0 && r0 + BR < r1) ta = a.t[r0 + BR];
-        prep(r0, t0, s0, k0, e0, ta, 0.0, 0);
-        load(r0 + BR, tn, sn, kn, en);
-        if (tid == 0 && r0 + 2 * BR < r1) tnn = a.t[r0 + 2 * BR];
+        if (tid == 0 && lo + BR < r1) ta = a.t[lo + BR];
+        prep(lo, t0, s0, k0, e0, ta, t_enter, 0);
+        load(lo + BR, tn, sn, kn, en);
+        if (tid == 0 && lo + 2 * BR < r1) tnn = a.t[lo + 2 * BR];
     }
 
-    for (int64_t b0 = r0; b0 < r1; b0 += BR) {
+    for (int64_t b0 = lo; b0 < hi; b0 += BR) {
 
         // ---- A: neighbours of every row; its ticket in its sink's bucket ----
         __syncthreads();
         RP_CLK(0);   // loop top, barrier 1
-        const int last = (int)((r1 - b0) < BR ? (r1 - b0) : BR);
+        const int last = (int)((hi - b0) < BR ? (hi - b0) : BR);
         const double t_last = tb[last];
         const int64_t e_last = has_eid ? eb[last] : 0;
         bool valid[R], start[R], endg[R];
@@ -415,7 +576,7 @@ __device__ __forceinline__ void rp_fast_body(RpArgs a)
         for (int r = 0; r < R; ++r) {
             const int row = tid * R + r;
             const int64_t i = b0 + row;
-            valid[r] = i < r1;
+            valid[r] = i < hi;
             ti[r] = tb[1 + row];
             const double t_prev = tb[row];
             tnx[r] = tb[row + 2];
@@ -423,7 +584,7 @@ __device__ __forceinline__ void rp_fast_body(RpArgs a)
             start[r] = valid[r] && (first_row || ti[r] != t_prev);
             endg[r] = valid[r] && (i == r1 - 1 || tnx[r] != ti[r]);
             ticket[r] = valid[r] ? bk_add(tst + slot_c[r]) : 0;   // rows of this sink before me: unordered
-            if (valid[r] && !first_row && ti[r] < t_prev) misc[3] = 1;
+            if (!CHUNK && valid[r] && !first_row && ti[r] < t_prev) misc[3] = 1;
             if (has_eid && valid[r]) {
                 const int64_t ei = eb[1 + row], e_prev = eb[row];
                 const bool fe = first_row || ei != e_prev;
@@ -433,7 +594,7 @@ __device__ __forceinline__ void rp_fast_body(RpArgs a)
             }
             st_loc += start[r];
         }
-        if (!GLOBAL && (misc[0] > (TIER == 0 ? RP_HMAX_S : RP_HMAX) || misc[9]))
+        if (TIER < 2 && (misc[0] > (TIER == 0 ? RP_HMAX_S : RP_HMAX) || misc[9]))
             aborted = true;   // uniform: read after the barrier
 
         // ---- B: t-group of every row (block scan of group starts) + event counts;
@@ -446,16 +607,20 @@ __device__ __forceinline__ void rp_fast_body(RpArgs a)
         }
         if (lane == 63) {
             ws32[w] = st_incl;
-            ws32[16 + w] = nbo;
-            ws32[32 + w] = nbw;
+            if constexpr (!CHUNK) {
+                ws32[16 + w] = nbo;
+                ws32[32 + w] = nbw;
+            }
         }
         RP_CLK(2);   // A: neighbours, tickets, group-start scan
         __syncthreads();
-        if (aborted) break;
-        int st_pre, st_tot, n_ev_own, n_ev_world, dummy;
+        if (!CHUNK && aborted) break;
+        int st_pre, st_tot, n_ev_own = 0, n_ev_world = 0, dummy;
         totals_add(ws32, w, st_pre, st_tot);
-        totals_add(ws32 + 16, w, dummy, n_ev_own);
-        totals_add(ws32 + 32, w, dummy, n_ev_world);
+        if constexpr (!CHUNK) {
+            totals_add(ws32 + 16, w, dummy, n_ev_own);
+            totals_add(ws32 + 32, w, dummy, n_ev_world);
+        }
         int64_t G[R];   // each row's t-group (pivot row index)
         {
             int64_t g = Gc + (int64_t)(st_pre + st_incl - st_loc) - 1;
@@ -672,20 +837,26 @@ __device__ __forceinline__ void rp_fast_body(RpArgs a)
         for (int q = 0; q < NK; ++q) carry.c[q] += tot.c[q];
         Gc += st_tot;
         if (tid == 0) {
-            misc[5] += n_ev_own;
-            misc[6] += n_ev_world;
+            if constexpr (!CHUNK) {
+                misc[5] += n_ev_own;
+                misc[6] += n_ev_world;
+            }
             misc[8] = 0;   // bucket allocator (read in B, two barriers ago)
         }
         RP_CLK(7);   // D2: barrier 5, block totals, pivot-row stores
-        if (misc[3]) break;   // unsorted (set in A, read after barriers): the df is rejected
+        if (!CHUNK && misc[3]) break;   // unsorted (set in A, read after barriers): the df is rejected
     }
 #ifdef RQ_PHASE_CLOCK
-    if (lane == 0 && a.clk)
+    if (!CHUNK && lane == 0 && a.clk)
         for (int q = 0; q < 8; ++q) atomicAdd(&a.clk[q], ck[q]);
 #endif
 #undef RP_CLK
 
     __syncthreads();
+    if constexpr (CHUNK) {   // a chunk's whole report: rq_rc_sum and rq_rc_scan wrote the rest
+        if (tid == 0 && misc[2]) atomicOr(&inf->flags, RP_FALLBACK);
+        return;
+    }
     if (aborted) {
         if (tid == 0) atomicOr(&inf->flags, TIER == 0 ? RP_MID : RP_GLOBAL);
         return;
@@ -1061,36 +1232,12 @@ __global__ __launch_bounds__(64) void rq_rp_seq(RpArgs a)
 //                t-group starts, first-of-event counts, unsorted / event-id checks
 //   rq_rc_scan   per sink, a wave scans the chunk functions: the state every chunk
 //                enters with; per dataframe the t-group base of every chunk
-//   rq_rc_apply  every chunk replays its rows exactly as rq_rp_fast does, starting from
+//   rq_rc_apply  every chunk replays its rows in rq_rp_fast's batch body, starting from
 //                those states and from the pivot row they sum to
 //   rq_rc_keys   unique sink ids of dataframes with a pivot mean, for rq_rp_seq
 // A dataframe with more than RC_S unique sinks (or the INT64_MIN id) is flagged
 // RP_CSKIP and left to rq_rp_fast.
 // ============================================================================
-__device__ __forceinline__ int64_t rc_df_of_chunk(const RpArgs& a, int64_t c)
-{
-    int64_t lo = 0, hi = a.n_df;   // the last d with cbase[d] <= c (empty dfs share a base)
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a.cbase[mid] <= c) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-constexpr int RC_HBITS = 13;   // log2(RC_HT)
-static_assert((1 << RC_HBITS) == RC_HT, "RC_HT");
-static_assert(RC_L % RP_B == 0, "chunks hold whole batches");
-constexpr int RC_SKIP = RP_BADOFF | RP_EMPTYDF | RP_CSKIP;
-
-__device__ __forceinline__ int rc_dense(const uint64_t* hk, const int* hd, uint64_t k)
-{
-    uint32_t h = rp_hash(k, RC_HBITS);
-    for (int p = 0; p < RC_HT; ++p) {   // rq_rc_hash inserted every key (bounded all the same)
-        if (hk[h] == k) return hd[h];
-        h = (h + 1) & (RC_HT - 1);
-    }
-    return 0;
-}
-
 __global__ __launch_bounds__(1024) void rq_rc_plan(RpArgs a)
 {
     __shared__ int wtot[16];
@@ -1132,20 +1279,6 @@ __global__ __launch_bounds__(256) void rq_rc_clear(RpArgs a)
     const int64_t n = a.n_df * RC_HT;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
         a.ht_keys[i] = RP_EMPTY_KEY;
-}
-
-// the chunk of this block: df d, rows [c0, c1); false if the block has none
-__device__ __forceinline__ bool rc_chunk(const RpArgs& a, int64_t& d, int64_t& r0, int64_t& r1, int64_t& c0,
-                                         int64_t& c1)
-{
-    const int64_t c = blockIdx.x;
-    if (c >= a.cbase[a.n_df]) return false;
-    d = rc_df_of_chunk(a, c);
-    r0 = df_begin(a, d);
-    r1 = df_end(a, d);
-    c0 = r0 + (c - a.cbase[d]) * RC_L;
-    c1 = c0 + RC_L < r1 ? c0 + RC_L : r1;
-    return true;
 }
 
 __global__ __launch_bounds__(1024) void rq_rc_hash(RpArgs a)
@@ -1398,271 +1531,14 @@ __global__ __launch_bounds__(1024) void rq_rc_scan(RpArgs a)
     }
 }
 
+// every chunk replays its rows in the one batch body (rp_fast_body's chunk mode), one row
+// per thread, from the states rq_rc_scan left.  At least 7 waves per SIMD, as the kernel
+// had with a body of its own: without the bound the scheduler issues the recount loop's 16
+// LDS reads at once and takes 79-82 VGPRs (5-6 waves); with it 62-64 and no scratch
 template <int NK>
-__global__ __launch_bounds__(RP_B) void rq_rc_apply(RpArgs a)
+__global__ __launch_bounds__(RP_B) __attribute__((amdgpu_waves_per_eu(7))) void rq_rc_apply(RpArgs a)
 {
-    int64_t d, r0, r1, c0, c1;
-    if (!rc_chunk(a, d, r0, r1, c0, c1)) return;
-    RpInfo* inf = a.info + d;
-    if (inf->flags & (RC_SKIP | RP_UNSORTED)) return;
-    const int64_t c = blockIdx.x;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int S = inf->S;
-    const uint64_t* hk = a.ht_keys + d * RC_HT;
-    const int* hd = a.ht_dense + d * RC_HT;
-
-    extern __shared__ __align__(16) unsigned char rc_smem[];
-    unsigned char* sp = rc_smem;
-    auto carve = [&](size_t bytes) {
-        unsigned char* p = sp;
-        sp += (bytes + 15) & ~(size_t)15;
-        return p;
-    };
-    double* tb = reinterpret_cast<double*>(carve(8 * (RP_B + 2)));       // [0] prev, [1+i], [RP_B+1] next
-    int* gb = reinterpret_cast<int*>(carve(4 * RP_B));                    // t-group of row i
-    int* lst = reinterpret_cast<int*>(carve(4 * RP_B));                   // sink buckets: rows
-    int64_t* wsum = reinterpret_cast<int64_t*>(carve(8 * 16));            // wave totals (int64)
-    int* ws32 = reinterpret_cast<int*>(carve(4 * 16 * (NK + 6)));         // wave totals (int)
-    int* misc = reinterpret_cast<int*>(carve(4 * 16));                    // [2] dup, [8] bucket allocator
-    RpSlot* tst = reinterpret_cast<RpSlot*>(carve(sizeof(RpSlot) * RC_S));
-
-    int km1[NK];
-#pragma unroll
-    for (int q = 0; q < NK; ++q) km1[q] = a.Ks[q] - 1;
-
-    // every sink's state entering the chunk, and the pivot row it sums to
-    const RcState* stin = a.state + c * RC_S;
-    const double t_bnd = c0 > r0 ? a.t[c0 - 1] : 0.0;
-    const bool spans = c0 > r0 && a.t[c0] == t_bnd;   // the chunk continues the previous t-group
-    const int64_t G0 = a.gbase[c];
-    int64_t ps = 0;
-    int pv = 0, pc[NK];
-#pragma unroll
-    for (int q = 0; q < NK; ++q) pc[q] = 0;
-    for (int s = tid; s < S; s += RP_B) {
-        const RcState e = stin[s];
-        if (e.r >= 0) {
-            // cnt = r + 1, lastown = 1: the next row's rank is r + 1; a cell in the
-            // spanning t-group keeps its group (a second row there is a pivot mean)
-            tst[s] = RpSlot{e.r + 1, 1, (spans && e.last_t == t_bnd) ? (int)(G0 - 1) : -1, 0};
-            ps += e.r;
-            pv += 1;
-#pragma unroll
-            for (int q = 0; q < NK; ++q) pc[q] += e.r <= km1[q] ? 1 : 0;
-        } else {
-            tst[s] = RpSlot{0, 0, -1, 0};
-        }
-    }
-    if (tid < 16) misc[tid] = 0;
-    {
-        int64_t s64 = ps;   // this wave's sum (int64 butterfly)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s64 += __shfl_xor(s64, o, 64);
-        const int sv = scan_add_i32(pv);
-        if (lane == 63) {
-            wsum[w] = s64;
-            ws32[80 + w] = sv;
-        }
-#pragma unroll
-        for (int q = 0; q < NK; ++q) {
-            const int sq = scan_add_i32(pc[q]);
-            if (lane == 63) ws32[96 + 16 * q + w] = sq;
-        }
-    }
-    __syncthreads();
-    RpAcc<NK> carry;
-    {
-        int64_t pre64;
-        int pre;
-        totals_add(wsum, w, pre64, carry.s);
-        totals_add(ws32 + 80, w, pre, carry.v);
-#pragma unroll
-        for (int q = 0; q < NK; ++q) totals_add(ws32 + 96 + 16 * q, w, pre, carry.c[q]);
-    }
-    int64_t Gc = G0;
-    __syncthreads();   // totals read before the batch loop reuses them
-
-    bool own_c = false;
-    int slot_c = 0;
-    auto prep = [&](int64_t nb0, double t_, int64_t s_, int64_t k_, double t_after, double t_before) {
-        const bool v = nb0 + tid < c1;
-        tb[1 + tid] = v ? t_ : 0.0;
-        if (tid == 0) {
-            tb[0] = t_before;
-            tb[RP_B + 1] = t_after;
-        }
-        own_c = v && s_ == a.src_id;
-        slot_c = v ? rc_dense(hk, hd, (uint64_t)k_) : 0;
-    };
-    {
-        const int64_t i0 = c0 + tid;
-        double t0 = 0.0, ta = 0.0;
-        int64_t s0 = 0, k0 = 0;
-        if (i0 < c1) {
-            t0 = a.t[i0];
-            s0 = a.src[i0];
-            k0 = a.sink[i0];
-        }
-        if (tid == 0 && c0 + RP_B < r1) ta = a.t[c0 + RP_B];
-        prep(c0, t0, s0, k0, ta, t_bnd);
-    }
-    // the next batch's row: loaded in the middle of the batch before, after its prep and
-    // before its pivot-row stores (rp_fast_body), at a clamped index (prep masks past c1)
-    double tn, tnn = 0.0;
-    int64_t sn, kn;
-    auto load_next = [&](int64_t nb0) __attribute__((always_inline)) {
-        const int64_t in = nb0 + tid;
-        const int64_t ic = in < c1 ? in : c1 - 1;   // c1 > c0: the loop runs
-        tn = a.t[ic];
-        sn = a.src[ic];
-        kn = a.sink[ic];
-        tnn = 0.0;
-        if (tid == 0 && nb0 + RP_B < r1) tnn = a.t[nb0 + RP_B];
-    };
-    if (c1 > c0) load_next(c0 + RP_B);
-
-    for (int64_t b0 = c0; b0 < c1; b0 += RP_B) {
-        const int64_t i = b0 + tid;
-        const bool valid = i < c1;
-
-        // ---- A: neighbours of every row; its ticket in its sink's bucket ----
-        __syncthreads();
-        const int last = (int)((c1 - b0) < RP_B ? (c1 - b0) : RP_B);
-        const double ti = tb[1 + tid];
-        const double t_prev = tb[tid], t_next = tb[tid + 2];
-        const double t_last = tb[last];
-        const bool first_row = i == r0;
-        const bool start = valid && (first_row || ti != t_prev);
-        const bool endg = valid && (i == r1 - 1 || t_next != ti);
-        const bool own = own_c;
-        RpSlot* sl = tst + slot_c;
-        const int ticket = valid ? atomicAdd(&sl->bucket, 1) : 0;
-
-        // ---- B: t-group of every row (block scan of group starts); list space ----
-        const int st_incl = scan_add_i32((int)start);
-        if (lane == 63) ws32[w] = st_incl;
-        __syncthreads();
-        int st_pre, st_tot;
-        totals_add(ws32, w, st_pre, st_tot);
-        const int64_t G = Gc + (int64_t)(st_pre + st_incl) - 1;
-        gb[tid] = (int)G;
-        const RpSlot st0 = valid ? *sl : RpSlot{0, 0, -1, 0};
-        const int m = valid ? (st0.bucket & 0xFFF) : 0;
-        {   // list space: one allocator atomic per wave (rp_fast_body)
-            const int need = valid && m > 1 && ticket == 0 ? m : 0;
-            const int incl = scan_add_i32(need);
-            int wb = 0;
-            if (lane == 63 && incl > 0) wb = atomicAdd(&misc[8], incl);
-            if (need) sl->bucket = ((__builtin_amdgcn_readlane(wb, 63) + incl - need) << 12) | m;
-        }
-        __syncthreads();
-
-        // ---- C: my place among my sink's rows in this batch ----
-        int boff = 0;
-        if (valid && m > 1) {
-            boff = sl->bucket >> 12;
-            lst[boff + ticket] = 2 * tid + (own ? 1 : 0);   // row, own flag
-        }
-        __syncthreads();
-        int j = 0, pred = -1, own_le = own ? tid : -1, own_lt = -1;
-        auto visit = [&](int v) __attribute__((always_inline)) {
-            const int y = v >> 1;
-            if (y < tid) {
-                ++j;
-                pred = pred > y ? pred : y;
-                if (v & 1) {
-                    own_lt = own_lt > y ? own_lt : y;
-                    own_le = own_le > y ? own_le : y;
-                }
-            }
-        };
-        if (valid && m > 1) {
-            for (int k = 0; k < m; k += 2) {   // two entries per LDS wait
-                const int v0 = lst[boff + k];
-                const int v1 = k + 1 < m ? lst[boff + k + 1] : 0x7FFFFFFF;
-                visit(v0);
-                visit(v1);
-            }
-        }
-        int j_le = 0, j_lt = 0;
-        if (valid && m > 1 && (own_le >= 0 || own_lt >= 0)) {
-            for (int k = 0; k < m; ++k) {
-                const int y = lst[boff + k] >> 1;
-                j_le += y < own_le;
-                j_lt += y < own_lt;
-            }
-        } else if (own_le >= 0) {
-            j_le = j;
-        }
-        RpAcc<NK> x;
-        x.s = 0;
-        x.v = 0;
-#pragma unroll
-        for (int q = 0; q < NK; ++q) x.c[q] = 0;
-        if (valid) {
-            const int pos = st0.cnt + j + 1;
-            const int lastown = own_le >= 0 ? st0.cnt + j_le + 1 : st0.lastown;
-            const int rank = pos - lastown;
-            int prevrank, prevg;
-            if (j > 0) {
-                prevrank = (pos - 1) - (own_lt >= 0 ? st0.cnt + j_lt + 1 : st0.lastown);
-                prevg = gb[pred];
-            } else {
-                prevrank = st0.cnt > 0 ? st0.cnt - st0.lastown : -1;
-                prevg = st0.lastgroup;
-            }
-            if (prevg == (int)G) misc[2] = 1;   // two rows of one sink at one t: a pivot mean
-            const bool pnan = prevrank < 0;
-            x.s = rank - (pnan ? 0 : prevrank);
-            x.v = pnan ? 1 : 0;
-#pragma unroll
-            for (int q = 0; q < NK; ++q)
-                x.c[q] = (rank <= km1[q] ? 1 : 0) - ((!pnan && prevrank <= km1[q]) ? 1 : 0);
-            if (j == m - 1) {
-                sl->cnt = pos;
-                sl->lastown = lastown;
-                sl->lastgroup = (int)G;
-                sl->bucket = 0;
-            }
-        }
-        prep(b0 + RP_B, tn, sn, kn, tnn, t_last);
-        load_next(b0 + 2 * RP_B);
-
-        // ---- D: running totals in row order; the last row of a t-group emits its pivot row ----
-        x.s = scan_add_i64_of_i32((int)x.s);
-        x.v = scan_add_i32(x.v);
-#pragma unroll
-        for (int q = 0; q < NK; ++q) x.c[q] = scan_add_i32(x.c[q]);
-        if (lane == 63) {
-            wsum[w] = x.s;
-            ws32[80 + w] = x.v;
-#pragma unroll
-            for (int q = 0; q < NK; ++q) ws32[96 + 16 * q + w] = x.c[q];
-        }
-        __syncthreads();
-        RpAcc<NK> pre, tot;
-        totals_add(wsum, w, pre.s, tot.s);
-        totals_add(ws32 + 80, w, pre.v, tot.v);
-#pragma unroll
-        for (int q = 0; q < NK; ++q) totals_add(ws32 + 96 + 16 * q, w, pre.c[q], tot.c[q]);
-        if (endg) {
-            const int64_t row = r0 + G;
-            a.rows_dt[row] = (i == r1 - 1 ? a.end : t_next) - ti;
-            a.rows_sum[row] = (double)(carry.s + pre.s + x.s);
-            a.rows_valid[row] = (uint32_t)(carry.v + pre.v + x.v);
-#pragma unroll
-            for (int q = 0; q < NK; ++q) a.rows_cnt[row * NK + q] = (uint32_t)(carry.c[q] + pre.c[q] + x.c[q]);
-        }
-        carry.s += tot.s;
-        carry.v += tot.v;
-#pragma unroll
-        for (int q = 0; q < NK; ++q) carry.c[q] += tot.c[q];
-        Gc += st_tot;
-        if (tid == 0) misc[8] = 0;   // bucket allocator (read in B, two barriers ago)
-    }
-    __syncthreads();
-    if (tid == 0 && misc[2]) atomicOr(&inf->flags, RP_FALLBACK);
+    rp_fast_body<NK, RP_TIER_CHUNK, 1>(a);
 }
 
 // unique sink ids of the chunked dataframes with a pivot mean (rq_rp_keys sorts them)
@@ -1753,25 +1629,6 @@ __global__ __launch_bounds__(256) void rq_rp_scan(RpArgs a)
 // launch wrappers
 // ============================================================================
 namespace {
-template <int TIER>
-size_t rp_fast_lds(int nK, int R)
-{
-    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t br = (size_t)R * RP_B;
-    size_t s = al(8 * (br + 2)) + al(8 * (br + 1)) + al(4 * br) + al(4 * br) + al(8 * 16) +
-               al(4 * 16 * (nK + 6)) + al(4 * 16);
-    const size_t h = TIER == 0 ? RP_HS : RP_H;
-    if (TIER < 2) s += al(8 * (h + 1)) + al(sizeof(RpSlot) * (h + 1));
-    return s;
-}
-
-size_t rc_apply_lds(int nK)
-{
-    auto al = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    return al(8 * (RP_B + 2)) + al(4 * RP_B) + al(4 * RP_B) + al(8 * 16) + al(4 * 16 * (nK + 6)) +
-           al(4 * 16) + al(sizeof(RpSlot) * RC_S);
-}
-
 int rp_num_cus()
 {
     static thread_local int dev = -1, cus = 0;
@@ -1794,16 +1651,16 @@ hipError_t rp_launch_t(const RpArgs& a, int phase, hipStream_t s)
     switch (phase) {
     case RP_PHASE_SMALL:
         if constexpr (NK <= RP_SMALL_NK) {
-            if (few) hipLaunchKernelGGL((rq_rp_fast_s<NK, RP_RFEW>), dim3(nd), dim3(RP_B), rp_fast_lds<0>(NK, RP_RFEW), s, a);
-            else hipLaunchKernelGGL((rq_rp_fast_s<NK, 1>), dim3(nd), dim3(RP_B), rp_fast_lds<0>(NK, 1), s, a);
+            if (few) hipLaunchKernelGGL((rq_rp_fast_s<NK, RP_RFEW>), dim3(nd), dim3(RP_B), RpLds(0, NK, RP_RFEW).bytes, s, a);
+            else hipLaunchKernelGGL((rq_rp_fast_s<NK, 1>), dim3(nd), dim3(RP_B), RpLds(0, NK, 1).bytes, s, a);
         }
         break;
     case RP_PHASE_FAST:   // the full table's LDS keeps one workgroup per CU anyway
-        hipLaunchKernelGGL((rq_rp_fast<NK, false, 2>), dim3(nd), dim3(RP_B), rp_fast_lds<1>(NK, 2), s, a);
+        hipLaunchKernelGGL((rq_rp_fast<NK, false, 2>), dim3(nd), dim3(RP_B), RpLds(1, NK, 2).bytes, s, a);
         break;
     case RP_PHASE_GLOBAL:
-        if (few) hipLaunchKernelGGL((rq_rp_fast<NK, true, 2>), dim3(nd), dim3(RP_B), rp_fast_lds<2>(NK, 2), s, a);
-        else hipLaunchKernelGGL((rq_rp_fast<NK, true, 1>), dim3(nd), dim3(RP_B), rp_fast_lds<2>(NK, 1), s, a);
+        if (few) hipLaunchKernelGGL((rq_rp_fast<NK, true, 2>), dim3(nd), dim3(RP_B), RpLds(2, NK, 2).bytes, s, a);
+        else hipLaunchKernelGGL((rq_rp_fast<NK, true, 1>), dim3(nd), dim3(RP_B), RpLds(2, NK, 1).bytes, s, a);
         break;
     case RP_PHASE_KEYS:
         hipLaunchKernelGGL(rq_rp_keys, dim3(nd), dim3(RP_B), 0, s, a);
@@ -1827,8 +1684,7 @@ hipError_t rp_launch_t(const RpArgs& a, int phase, hipStream_t s)
         hipLaunchKernelGGL(rq_rc_dense, dim3(nd), dim3(1024), 0, s, a);
         hipLaunchKernelGGL(rq_rc_sum, dim3(mc), dim3(1024), 4 * RC_S * sizeof(int), s, a);
         hipLaunchKernelGGL(rq_rc_scan, dim3(nd, RC_S / 16), dim3(1024), 0, s, a);
-        const size_t lds = rc_apply_lds(NK);
-        hipLaunchKernelGGL((rq_rc_apply<NK>), dim3(mc), dim3(RP_B), lds, s, a);
+        hipLaunchKernelGGL((rq_rc_apply<NK>), dim3(mc), dim3(RP_B), RpLds(RP_TIER_CHUNK, NK, 1).bytes, s, a);
         hipLaunchKernelGGL(rq_rc_keys, dim3(nd), dim3(1024), 0, s, a);
         break;
     }

@@ -355,6 +355,9 @@ def wide_frame(n_sinks, rows, seed=0):
 # ---------------------------------------------------------------------------- batch boundaries
 BOUNDARY_LENGTHS = (1, 1023, 1024, 1025, 2047, 2048, 2049, 4096, 4097)
 BOUNDARY_KINDS = ("tgroup", "own_last", "one_sink", "split_event", "dup_across")
+# frames for the chunked path (chunks of 4096 rows): a second chunk of one row, two full
+# chunks (the last batch full, the last chunk ending with the frame), a last chunk of 8 rows
+CHUNK_EDGE_LENGTHS = (4097, 8192, 8200)
 
 
 def boundary_frame(n, kind, seed=0):

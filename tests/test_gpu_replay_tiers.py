@@ -279,15 +279,19 @@ def test_chunk_boundary_constructions(kind):
     """The same constructions at every multiple of 1024 rows of an 8200-row frame, so also
     at the chunk edges (RC_L = 4096 rows: rows 4096 and 8192), forced through the chunked
     path: a sink's entering state, the t-group a chunk continues and a duplicate cell whose
-    rows two chunks hold.  Equal to the one-workgroup path and to the oracle."""
+    rows two chunks hold.  Equal to the one-workgroup path and to the oracle.  Likewise
+    4097 rows (a second chunk of one row) and 8192 (two full chunks: the last batch full,
+    the last chunk ending with the frame), each for one, three and four Ks (rq_rc_apply<1>,
+    <3>, <4>)."""
     torch, O, L, U = _ctx()
-    df = RC.boundary_frame(8200, kind)
-    for Ks in ((1,), (1, 2, 5)):
-        exp, ecnt = _expect(O, df, Ks)
-        got_c, cnt_c = _abi(df, Ks, large=True, chunked=True)
-        got_o, cnt_o = _abi(df, Ks, large=True, chunked=False)
-        _same(got_c, cnt_c, exp, ecnt, ("chunked", Ks))
-        _same(got_o, cnt_o, exp, ecnt, ("one workgroup", Ks))
+    for n in RC.CHUNK_EDGE_LENGTHS:
+        df = RC.boundary_frame(n, kind)
+        for Ks in ((1,), (1, 2, 5), RC.KS_ALL):
+            exp, ecnt = _expect(O, df, Ks)
+            got_c, cnt_c = _abi(df, Ks, large=True, chunked=True)
+            got_o, cnt_o = _abi(df, Ks, large=True, chunked=False)
+            _same(got_c, cnt_c, exp, ecnt, ("chunked", n, Ks))
+            _same(got_o, cnt_o, exp, ecnt, ("one workgroup", n, Ks))
 
 
 # ---------------------------------------------------------------------------- chunked limits

@@ -175,7 +175,7 @@ def test_chunked_limit_frames(n_sinks):
 
 
 @pytest.mark.parametrize("kind", RC.BOUNDARY_KINDS)
-@pytest.mark.parametrize("n", RC.BOUNDARY_LENGTHS + (8200,))
+@pytest.mark.parametrize("n", RC.BOUNDARY_LENGTHS + (8192, 8200))
 def test_boundary_frames(n, kind):
     df = RC.boundary_frame(n, kind)
     assert len(df) == n
@@ -186,7 +186,9 @@ def test_boundary_frames(n, kind):
         return
     step = RC.BATCH
     if kind == "dup_across":   # only at the coarsest boundaries, and no other duplicate
-        step = {1025: 1024, 2047: 1024, 2048: 1024, 2049: 2048, 4096: 2048, 4097: 4096, 8200: 4096}.get(n, n)
+        step = {1025: 1024, 2047: 1024, 2048: 1024, 2049: 2048, 4096: 2048, 4097: 4096, 8192: 4096,
+                8200: 4096}.get(n, n)
+        assert n not in RC.CHUNK_EDGE_LENGTHS or step == RC.CHUNK_ROWS   # only at the chunk edge
         assert df.duplicated(["t", "sink_id"], keep=False).sum() == 2 * len(range(step, n, step))
     _check_live(df, dup=kind == "dup_across" and n > 1024)
     for b in range(step, n, step):
