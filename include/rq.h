@@ -50,6 +50,8 @@
  *                       for every replica of a batch of event logs at once
  *   rq_log_metrics_of   the same with src_id = any source of the graph, on the df or on
  *                       df[df.sink_id.isin(its followers)], several sources in one call
+ *   rq_log_metrics_slim, rq_log_metrics_of_slim   the two above for graphs of up to 19,400
+ *                       sinks (8-byte pivot cells), the same bits
  *   rq_log_game        Opt broadcasters among SimOpts.other_sources  opt_model.py:761,
  *                       each Opt.get_next_interval :502-544 in run_dynamic's loop :271-309
  *
@@ -698,6 +700,57 @@ int rq_log_metrics_of(rq_graph_t g, const int64_t* src_ids /* host [n_src] */, i
                       int64_t* out_counts,  /* device [n_rep][n_src][4] */
                       int32_t* status,      /* device [n_rep][n_src] */
                       void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* rq_log_metrics for graphs of up to RQ_LOG_METRICS_SLIM_MAX_SINKS sinks: the same
+ * time_in_top_k / average_rank / int_r_2 over rank_of_src_in_df's pivot table (utils.py:84-121,
+ * utils.py:38-56) and num_tweets_of's counts (utils.py:170-176), the same arguments, the same
+ * outputs bit for bit, the same validation order and statuses.  Two things differ:
+ *   1. a sink's state is 8 bytes of LDS, not 16: rank (i32), the tag of its last t-group + 1
+ *      (21 bits) and one bit that says the group has several rows of this sink.  While a group
+ *      has one row of a sink its row count is 1 and its rank sum is the rank, so nothing more
+ *      is kept; the 64-bit (rank sum << 24 | row count) of a group with several rows lives in
+ *      the workspace, one word per sink and block, written on the sink's second row in a
+ *      t-group and read only where the bit is set.  Every quotient and comparison gets the
+ *      operands rq_log_metrics gives it.  4,784 + 8 n + 6 ceil(n / 32) bytes fit the
+ *      workgroup's 160 KiB up to n = 19,426: the limit is 19,400;
+ *   2. rq_log_metrics_slim_workspace's bytes are rq_log_metrics_workspace's plus, per block,
+ *      8 * n_sinks rounded up to 16.
+ * RQ_EUNSUPPORTED, nothing launched, the workspace query answering the same: ev_cap > 2^20,
+ * duplicate edges, more than RQ_LOG_METRICS_SLIM_MAX_SINKS sinks.  After an event with a tie
+ * a block waits for its workspace stores before the next event.  rq_log_metrics and
+ * rq_log_metrics_of stay as they are, their limit included.
+ *   Added without an ABI version change (RQ_ABI_VERSION stays 6); a caller detects the
+ * functions by their symbols. */
+#define RQ_LOG_METRICS_SLIM_MAX_SINKS 19400
+int rq_log_metrics_slim_workspace(rq_graph_t g, int64_t n_rep, int64_t ev_cap, int32_t nK, size_t* bytes);
+int rq_log_metrics_slim(rq_graph_t g, const double* ev_t, const int32_t* ev_src,
+                        const int64_t* counts, int64_t n_rep, int64_t ev_cap,
+                        const int32_t* Ks, int32_t nK,   /* host, 1 <= nK <= 4, K >= 1 */
+                        double* metrics,       /* device [n_rep][nK + 2]: top_K..., avg_rank, r_2 */
+                        int64_t* out_counts,   /* device [n_rep][4] */
+                        int32_t* status,       /* device [n_rep] */
+                        void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* rq_log_metrics_of on the 8-byte cells of rq_log_metrics_slim: time_in_top_k(df, K, src_id=c),
+ * average_rank(df, src_id=c) and int_r_2 for any sources c (utils.py:84-121 take any src_id),
+ * on the log's dataframe or on the rows of c's followers (opt_model.py:505).  Arguments,
+ * outputs (bit for bit), validation order, statuses, the number of blocks and their shares of
+ * the (replica, source) items are rq_log_metrics_of's; the sink limit and the workspace
+ * (rq_log_metrics_of_workspace's bytes plus 8 * n_sinks rounded up to 16 per block) are
+ * rq_log_metrics_slim's.  In scope RQ_LOG_OF_OWN the follower bits are built where the cells
+ * will be, as there.
+ *   Added without an ABI version change (RQ_ABI_VERSION stays 6); a caller detects the
+ * functions by their symbols. */
+int rq_log_metrics_of_slim_workspace(rq_graph_t g, int32_t n_src, int64_t n_rep, int64_t ev_cap,
+                                     int32_t nK, size_t* bytes);
+int rq_log_metrics_of_slim(rq_graph_t g, const int64_t* src_ids /* host [n_src] */, int32_t n_src,
+                           int32_t scope, const double* ev_t, const int32_t* ev_src,
+                           const int64_t* counts, int64_t n_rep, int64_t ev_cap,
+                           const int32_t* Ks, int32_t nK,
+                           double* metrics,      /* device [n_rep][n_src][nK + 2] */
+                           int64_t* out_counts,  /* device [n_rep][n_src][4] */
+                           int32_t* status,      /* device [n_rep][n_src] */
+                           void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /* Competing RedQueen broadcasters (Opt among SimOpts.other_sources, opt_model.py:493-544,
  * :761): several Opts -- the PLAYERS -- post against each other and against an exogenous

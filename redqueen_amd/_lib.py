@@ -70,6 +70,7 @@ TIMELINE_MAX_SINKS = 12288   # RQ_TIMELINE_MAX_SINKS
 FOLLOWERS_TILED_MAX_SINKS = 40960   # RQ_FOLLOWERS_TILED_MAX_SINKS
 RANK_HIST_MAX_RANKS = 255    # RQ_RANK_HIST_MAX_RANKS
 LOG_METRICS_MAX_SINKS = 9800   # RQ_LOG_METRICS_MAX_SINKS
+LOG_METRICS_SLIM_MAX_SINKS = 19400   # RQ_LOG_METRICS_SLIM_MAX_SINKS
 LOG_OF_DF, LOG_OF_OWN = 0, 1   # RQ_LOG_OF_DF, RQ_LOG_OF_OWN: the scope of rq_log_metrics_of
 LOG_OF_MAX_SRC = 64            # RQ_LOG_OF_MAX_SRC
 
@@ -132,6 +133,9 @@ _lib = None
 OPTIONAL = ("rq_log_metrics_of_workspace", "rq_log_metrics_of")
 # the replay of dataframes in any row order (utils.replay_columns(unsorted="sort")), optional likewise
 OPTIONAL_UNSORTED = ("rq_replay_unsorted_workspace_size", "rq_metrics_replay_unsorted")
+# rq_log_metrics / rq_log_metrics_of on 8-byte cells (up to LOG_METRICS_SLIM_MAX_SINKS sinks), optional likewise
+OPTIONAL_SLIM = ("rq_log_metrics_slim_workspace", "rq_log_metrics_slim",
+                 "rq_log_metrics_of_slim_workspace", "rq_log_metrics_of_slim")
 
 
 def has(fn):
@@ -211,6 +215,17 @@ def lib():
         L.rq_log_metrics_of.argtypes = [_P, _pi64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, C.c_int64,
                                         _pi32, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]
         L.rq_log_metrics_of.restype = C.c_int
+    if all(hasattr(L, fn) for fn in OPTIONAL_SLIM):
+        L.rq_log_metrics_slim_workspace.argtypes = L.rq_log_metrics_workspace.argtypes
+        L.rq_log_metrics_slim_workspace.restype = C.c_int
+        L.rq_log_metrics_slim.argtypes = L.rq_log_metrics.argtypes
+        L.rq_log_metrics_slim.restype = C.c_int
+        L.rq_log_metrics_of_slim_workspace.argtypes = [_P, C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                                       C.POINTER(C.c_size_t)]
+        L.rq_log_metrics_of_slim_workspace.restype = C.c_int
+        L.rq_log_metrics_of_slim.argtypes = [_P, _pi64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int64, C.c_int64,
+                                             _pi32, C.c_int32, _P, _P, _P, _P, C.c_size_t, _P]
+        L.rq_log_metrics_of_slim.restype = C.c_int
     if all(hasattr(L, fn) for fn in OPTIONAL_UNSORTED):
         L.rq_replay_unsorted_workspace_size.argtypes = L.rq_replay_workspace_size.argtypes
         L.rq_replay_unsorted_workspace_size.restype = C.c_int
@@ -274,7 +289,9 @@ EXPORTED = ["rq_abi_version", "rq_strerror", "rq_graph_build", "rq_graph_free", 
             "rq_u_int", "rq_log_rows", "rq_log_expand", "rq_log_timeline", "rq_log_followers",
             "rq_log_followers_tiled_workspace", "rq_log_followers_tiled",
             "rq_log_rank_hist", "rq_log_metrics_workspace", "rq_log_metrics",
-            "rq_log_metrics_of_workspace", "rq_log_metrics_of", "rq_log_game_workspace", "rq_log_game",
+            "rq_log_metrics_of_workspace", "rq_log_metrics_of", "rq_log_metrics_slim_workspace",
+            "rq_log_metrics_slim", "rq_log_metrics_of_slim_workspace", "rq_log_metrics_of_slim",
+            "rq_log_game_workspace", "rq_log_game",
             "rq_timing", "rq_timing_read"]
 # rq_log_followers_max_sinks, rq_log_followers_tile_sinks and rq_log_game_table_in_lds return
 # int32_t, no status

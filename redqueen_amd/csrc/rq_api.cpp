@@ -1297,27 +1297,77 @@ int rq_log_rank_hist(rq_graph_t g, const double* ev_t, const int32_t* ev_src, co
 // the blocks of an rq_log_metrics launch: one per replica up to RQ_LM_SLOTS
 static int64_t log_metrics_slots(int64_t n_rep) { return n_rep < RQ_LM_SLOTS ? n_rep : RQ_LM_SLOTS; }
 
-// what rq_log_metrics and its workspace query refuse alike
-static int log_metrics_check(rq_graph_t g, int64_t n_rep, int64_t ev_cap, int32_t nK)
+// what rq_log_metrics and its workspace query refuse alike; slim: the entries on 8-byte cells,
+// which differ in the sink limit and the LDS formula only
+static int log_metrics_check(rq_graph_t g, int64_t n_rep, int64_t ev_cap, int32_t nK, bool slim = false)
 {
     if (!g || n_rep < 1 || n_rep > INT32_MAX || ev_cap < 1) return RQ_EINVAL;
     if (nK < 1 || nK > RQ_MAX_K) return RQ_EINVAL;
-    if (log_unsupported(g, RQ_LOG_METRICS_MAX_SINKS)) return RQ_EUNSUPPORTED;
+    if (log_unsupported(g, slim ? RQ_LOG_METRICS_SLIM_MAX_SINKS : RQ_LOG_METRICS_MAX_SINKS)) return RQ_EUNSUPPORTED;
     // a cell counts a column's rows in a t-group in 24 bits and sums their ranks in 40: logs
     // with room for more events are not played here (the dataframe replay takes any)
     if (ev_cap > RQ_LM_MAX_EV_CAP) return RQ_EUNSUPPORTED;
     // the stream bits share the cells' LDS: past ~1.2 million streams they outgrow it
-    if (rq_log_metrics_lds_bytes(g->n_sinks, g->n_str) > RQ_LM_LDS_BYTES) return RQ_EUNSUPPORTED;
+    const size_t lds = slim ? rq_log_metrics_slim_lds_bytes(g->n_sinks, g->n_str)
+                            : rq_log_metrics_lds_bytes(g->n_sinks, g->n_str);
+    if (lds > RQ_LM_LDS_BYTES) return RQ_EUNSUPPORTED;
     return RQ_OK;
+}
+
+// a block's slot of the workspace: its pivot rows and, behind them, the slim cells' spill words
+static size_t log_metrics_slot(rq_graph_t g, int64_t ev_cap, int32_t nK, bool slim)
+{
+    return slim ? rq_log_metrics_slim_slot_bytes(ev_cap, nK, g->n_sinks) : rq_log_metrics_slot_bytes(ev_cap, nK);
+}
+
+// what both cell layouts hand their kernels once the call is accepted
+static void log_metrics_fill(LogMetricsArgs& a, rq_graph_t g, const double* ev_t, const int32_t* ev_src,
+                             const int64_t* counts, int64_t n_rep, int64_t ev_cap, int32_t nK, double* metrics,
+                             int64_t* out_counts, int32_t* status, void* workspace, bool slim)
+{
+    a.log = log_view(g, ev_t, ev_src, counts, n_rep, ev_cap);
+    a.nK = nK;
+    a.state_bytes = slim ? rq_log_metrics_slim_state_bytes(g->n_sinks, g->n_str)
+                         : rq_log_metrics_state_bytes(g->n_sinks, g->n_str);
+    a.spill_off = slim ? rq_log_metrics_slot_bytes(ev_cap, nK) : 0;
+    a.rows = static_cast<char*>(workspace);
+    a.metrics = metrics;
+    a.out_counts = out_counts;
+    a.status = status;
+}
+
+static int log_metrics_workspace(rq_graph_t g, int64_t n_rep, int64_t ev_cap, int32_t nK, size_t* bytes, bool slim)
+{
+    if (!bytes) return RQ_EINVAL;
+    const int rc = log_metrics_check(g, n_rep, ev_cap, nK, slim);
+    if (rc != RQ_OK) return rc;
+    *bytes = (size_t)log_metrics_slots(n_rep) * log_metrics_slot(g, ev_cap, nK, slim);
+    return RQ_OK;
+}
+
+static int log_metrics_run(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const int64_t* counts,
+                           int64_t n_rep, int64_t ev_cap, const int32_t* Ks, int32_t nK, double* metrics,
+                           int64_t* out_counts, int32_t* status, void* workspace, size_t workspace_bytes,
+                           void* hip_stream, bool slim)
+{
+    if (!g || !ev_t || !ev_src || !counts || !metrics || !out_counts || !status || !workspace) return RQ_EINVAL;
+    LogMetricsArgs a{};
+    if (!copy_ks(Ks, nK, a.Ks)) return RQ_EINVAL;
+    const int rc = log_metrics_check(g, n_rep, ev_cap, nK, slim);
+    if (rc != RQ_OK) return rc;
+    a.n_slots = (int)log_metrics_slots(n_rep);
+    a.slot_bytes = log_metrics_slot(g, ev_cap, nK, slim);
+    if (workspace_bytes < (size_t)a.n_slots * a.slot_bytes || (reinterpret_cast<uintptr_t>(workspace) & 7))
+        return RQ_EINVAL;
+    log_metrics_fill(a, g, ev_t, ev_src, counts, n_rep, ev_cap, nK, metrics, out_counts, status, workspace, slim);
+    hipStream_t st = (hipStream_t)hip_stream;
+    TimedLaunch tl(K_REPLAY, st);
+    return rq_launch_log_metrics(a, st, slim) == hipSuccess ? RQ_OK : RQ_EHIP;
 }
 
 int rq_log_metrics_workspace(rq_graph_t g, int64_t n_rep, int64_t ev_cap, int32_t nK, size_t* bytes)
 {
-    if (!bytes) return RQ_EINVAL;
-    const int rc = log_metrics_check(g, n_rep, ev_cap, nK);
-    if (rc != RQ_OK) return rc;
-    *bytes = (size_t)log_metrics_slots(n_rep) * rq_log_metrics_slot_bytes(ev_cap, nK);
-    return RQ_OK;
+    return log_metrics_workspace(g, n_rep, ev_cap, nK, bytes, false);
 }
 
 int rq_log_metrics(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const int64_t* counts,
@@ -1325,25 +1375,22 @@ int rq_log_metrics(rq_graph_t g, const double* ev_t, const int32_t* ev_src, cons
                    int64_t* out_counts, int32_t* status, void* workspace, size_t workspace_bytes,
                    void* hip_stream)
 {
-    if (!g || !ev_t || !ev_src || !counts || !metrics || !out_counts || !status || !workspace) return RQ_EINVAL;
-    LogMetricsArgs a{};
-    if (!copy_ks(Ks, nK, a.Ks)) return RQ_EINVAL;
-    const int rc = log_metrics_check(g, n_rep, ev_cap, nK);
-    if (rc != RQ_OK) return rc;
-    a.n_slots = (int)log_metrics_slots(n_rep);
-    a.slot_bytes = rq_log_metrics_slot_bytes(ev_cap, nK);
-    if (workspace_bytes < (size_t)a.n_slots * a.slot_bytes || (reinterpret_cast<uintptr_t>(workspace) & 7))
-        return RQ_EINVAL;
-    a.log = log_view(g, ev_t, ev_src, counts, n_rep, ev_cap);
-    a.nK = nK;
-    a.state_bytes = rq_log_metrics_state_bytes(g->n_sinks, g->n_str);
-    a.rows = static_cast<char*>(workspace);
-    a.metrics = metrics;
-    a.out_counts = out_counts;
-    a.status = status;
-    hipStream_t st = (hipStream_t)hip_stream;
-    TimedLaunch tl(K_REPLAY, st);
-    return rq_launch_log_metrics(a, st) == hipSuccess ? RQ_OK : RQ_EHIP;
+    return log_metrics_run(g, ev_t, ev_src, counts, n_rep, ev_cap, Ks, nK, metrics, out_counts, status, workspace,
+                           workspace_bytes, hip_stream, false);
+}
+
+int rq_log_metrics_slim_workspace(rq_graph_t g, int64_t n_rep, int64_t ev_cap, int32_t nK, size_t* bytes)
+{
+    return log_metrics_workspace(g, n_rep, ev_cap, nK, bytes, true);
+}
+
+int rq_log_metrics_slim(rq_graph_t g, const double* ev_t, const int32_t* ev_src, const int64_t* counts,
+                        int64_t n_rep, int64_t ev_cap, const int32_t* Ks, int32_t nK, double* metrics,
+                        int64_t* out_counts, int32_t* status, void* workspace, size_t workspace_bytes,
+                        void* hip_stream)
+{
+    return log_metrics_run(g, ev_t, ev_src, counts, n_rep, ev_cap, Ks, nK, metrics, out_counts, status, workspace,
+                           workspace_bytes, hip_stream, true);
 }
 
 // the blocks of an rq_log_metrics_of launch: one per (replica, source) up to the slot count
@@ -1353,20 +1400,20 @@ static int64_t log_of_slots(int64_t n_rep, int32_t n_src)
     return rqh::log_of_blocks(n_rep, n_src, slots);
 }
 
-int rq_log_metrics_of_workspace(rq_graph_t g, int32_t n_src, int64_t n_rep, int64_t ev_cap, int32_t nK,
-                                size_t* bytes)
+static int log_metrics_of_workspace(rq_graph_t g, int32_t n_src, int64_t n_rep, int64_t ev_cap, int32_t nK,
+                                    size_t* bytes, bool slim)
 {
     if (!bytes || n_src < 1 || n_src > RQ_LOG_OF_MAX_SRC) return RQ_EINVAL;
-    const int rc = log_metrics_check(g, n_rep, ev_cap, nK);
+    const int rc = log_metrics_check(g, n_rep, ev_cap, nK, slim);
     if (rc != RQ_OK) return rc;
-    *bytes = (size_t)log_of_slots(n_rep, n_src) * rq_log_metrics_slot_bytes(ev_cap, nK);
+    *bytes = (size_t)log_of_slots(n_rep, n_src) * log_metrics_slot(g, ev_cap, nK, slim);
     return RQ_OK;
 }
 
-int rq_log_metrics_of(rq_graph_t g, const int64_t* src_ids, int32_t n_src, int32_t scope, const double* ev_t,
-                      const int32_t* ev_src, const int64_t* counts, int64_t n_rep, int64_t ev_cap,
-                      const int32_t* Ks, int32_t nK, double* metrics, int64_t* out_counts, int32_t* status,
-                      void* workspace, size_t workspace_bytes, void* hip_stream)
+static int log_metrics_of_run(rq_graph_t g, const int64_t* src_ids, int32_t n_src, int32_t scope,
+                              const double* ev_t, const int32_t* ev_src, const int64_t* counts, int64_t n_rep,
+                              int64_t ev_cap, const int32_t* Ks, int32_t nK, double* metrics, int64_t* out_counts,
+                              int32_t* status, void* workspace, size_t workspace_bytes, void* hip_stream, bool slim)
 {
     if (!g || !src_ids || !ev_t || !ev_src || !counts || !metrics || !out_counts || !status || !workspace)
         return RQ_EINVAL;
@@ -1375,24 +1422,48 @@ int rq_log_metrics_of(rq_graph_t g, const int64_t* src_ids, int32_t n_src, int32
     LogMetricsArgs& a = b.m;
     if (rqh::log_of_streams(*g, src_ids, n_src, b.trk) != RQ_OK) return RQ_EINVAL;
     if (!copy_ks(Ks, nK, a.Ks)) return RQ_EINVAL;
-    const int rc = log_metrics_check(g, n_rep, ev_cap, nK);
+    const int rc = log_metrics_check(g, n_rep, ev_cap, nK, slim);
     if (rc != RQ_OK) return rc;
     a.n_slots = (int)log_of_slots(n_rep, n_src);
-    a.slot_bytes = rq_log_metrics_slot_bytes(ev_cap, nK);
+    a.slot_bytes = log_metrics_slot(g, ev_cap, nK, slim);
     if (workspace_bytes < (size_t)a.n_slots * a.slot_bytes || (reinterpret_cast<uintptr_t>(workspace) & 7))
         return RQ_EINVAL;
-    a.log = log_view(g, ev_t, ev_src, counts, n_rep, ev_cap);
-    a.nK = nK;
-    a.state_bytes = rq_log_metrics_state_bytes(g->n_sinks, g->n_str);
-    a.rows = static_cast<char*>(workspace);
-    a.metrics = metrics;
-    a.out_counts = out_counts;
-    a.status = status;
+    log_metrics_fill(a, g, ev_t, ev_src, counts, n_rep, ev_cap, nK, metrics, out_counts, status, workspace, slim);
     b.n_src = n_src;
     b.scope = scope;
     hipStream_t st = (hipStream_t)hip_stream;
     TimedLaunch tl(K_REPLAY, st);
-    return rq_launch_log_metrics_of(b, st) == hipSuccess ? RQ_OK : RQ_EHIP;
+    return rq_launch_log_metrics_of(b, st, slim) == hipSuccess ? RQ_OK : RQ_EHIP;
+}
+
+int rq_log_metrics_of_workspace(rq_graph_t g, int32_t n_src, int64_t n_rep, int64_t ev_cap, int32_t nK,
+                                size_t* bytes)
+{
+    return log_metrics_of_workspace(g, n_src, n_rep, ev_cap, nK, bytes, false);
+}
+
+int rq_log_metrics_of(rq_graph_t g, const int64_t* src_ids, int32_t n_src, int32_t scope, const double* ev_t,
+                      const int32_t* ev_src, const int64_t* counts, int64_t n_rep, int64_t ev_cap,
+                      const int32_t* Ks, int32_t nK, double* metrics, int64_t* out_counts, int32_t* status,
+                      void* workspace, size_t workspace_bytes, void* hip_stream)
+{
+    return log_metrics_of_run(g, src_ids, n_src, scope, ev_t, ev_src, counts, n_rep, ev_cap, Ks, nK, metrics,
+                              out_counts, status, workspace, workspace_bytes, hip_stream, false);
+}
+
+int rq_log_metrics_of_slim_workspace(rq_graph_t g, int32_t n_src, int64_t n_rep, int64_t ev_cap, int32_t nK,
+                                     size_t* bytes)
+{
+    return log_metrics_of_workspace(g, n_src, n_rep, ev_cap, nK, bytes, true);
+}
+
+int rq_log_metrics_of_slim(rq_graph_t g, const int64_t* src_ids, int32_t n_src, int32_t scope, const double* ev_t,
+                           const int32_t* ev_src, const int64_t* counts, int64_t n_rep, int64_t ev_cap,
+                           const int32_t* Ks, int32_t nK, double* metrics, int64_t* out_counts, int32_t* status,
+                           void* workspace, size_t workspace_bytes, void* hip_stream)
+{
+    return log_metrics_of_run(g, src_ids, n_src, scope, ev_t, ev_src, counts, n_rep, ev_cap, Ks, nK, metrics,
+                              out_counts, status, workspace, workspace_bytes, hip_stream, true);
 }
 
 int rq_log_game_workspace(rq_graph_t g, int32_t n_players, size_t* bytes)

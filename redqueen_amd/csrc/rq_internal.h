@@ -484,19 +484,50 @@ inline size_t rq_log_metrics_slot_bytes(int64_t ev_cap, int nK)
 {
     return ((size_t)ev_cap * (20 + 4 * (size_t)nK) + 15) / 16 * 16;
 }
+// The slim entries (rq_log_metrics_slim, rq_log_metrics_of_slim): a column's state is 8 bytes
+// of LDS -- rank, tag and one bit "several rows in the tag's t-group" -- and the 64-bit
+// sum << 24 | count of such a group lives in the block's slot of the workspace, one word per
+// column behind the slot's rows (rq_log_metrics.hip).
+constexpr int RQ_LM_SLIM_CELL_BYTES = 8;
+inline size_t rq_log_metrics_slim_state_bytes(int n_sinks, int n_str)
+{
+    const size_t cells = (size_t)n_sinks * RQ_LM_SLIM_CELL_BYTES;
+    const size_t sbits = (((size_t)n_str + 31) / 32 * 4 + 15) / 16 * 16;
+    return cells > sbits ? cells : sbits;
+}
+constexpr size_t rq_log_metrics_slim_cells_lds_bytes(size_t n_sinks)   // the formula while the cells outgrow the stream bits
+{
+    return RQ_LM_SCRATCH_BYTES + n_sinks * RQ_LM_SLIM_CELL_BYTES + 4 * ((n_sinks + 31) / 32) +
+           (2 * ((n_sinks + 31) / 32) + 3) / 4 * 4;
+}
+inline size_t rq_log_metrics_slim_lds_bytes(int n_sinks, int n_str)
+{
+    const size_t W = ((size_t)n_sinks + 31) / 32;
+    return RQ_LM_SCRATCH_BYTES + rq_log_metrics_slim_state_bytes(n_sinks, n_str) + 4 * W + (2 * W + 3) / 4 * 4;
+}
+static_assert(rq_log_metrics_slim_cells_lds_bytes(RQ_LOG_METRICS_SLIM_MAX_SINKS) <= RQ_LM_LDS_BYTES,
+              "RQ_LOG_METRICS_SLIM_MAX_SINKS sinks of 8-byte cells fit one workgroup's LDS");
+// the spill words of a slot: one per graph sink (a replica has at most that many columns)
+inline size_t rq_log_metrics_spill_bytes(int n_sinks) { return ((size_t)n_sinks * 8 + 15) / 16 * 16; }
+inline size_t rq_log_metrics_slim_slot_bytes(int64_t ev_cap, int nK, int n_sinks)
+{
+    return rq_log_metrics_slot_bytes(ev_cap, nK) + rq_log_metrics_spill_bytes(n_sinks);
+}
 struct LogMetricsArgs {
     LogView log;
     int Ks[RQ_MAX_K];
     int nK;
     int n_slots;              // blocks; block b plays replicas b, b + n_slots, ...
-    size_t state_bytes;       // rq_log_metrics_state_bytes
-    size_t slot_bytes;        // rq_log_metrics_slot_bytes
+    size_t state_bytes;       // rq_log_metrics_state_bytes / rq_log_metrics_slim_state_bytes
+    size_t slot_bytes;        // rq_log_metrics_slot_bytes / rq_log_metrics_slim_slot_bytes
+    size_t spill_off;         // slim: the spill words' offset in a slot (rq_log_metrics_slot_bytes); else 0
     char* rows;               // workspace [n_slots][slot_bytes]
     double* metrics;          // [n_rep][nK + 2]
     int64_t* out_counts;      // [n_rep][4]
     int32_t* status;          // [n_rep]
 };
-hipError_t rq_launch_log_metrics(const LogMetricsArgs& a, hipStream_t s);
+// slim: the 8-byte cells (state_bytes, slot_bytes and spill_off sized for them)
+hipError_t rq_launch_log_metrics(const LogMetricsArgs& a, hipStream_t s, bool slim = false);
 
 // rq_log_metrics_of: the same play for n_src tracked streams.  The work items (replica,
 // tracked source) are dealt to m.n_slots blocks in contiguous ranges, so a block plays, per
@@ -513,7 +544,7 @@ struct LogMetricsOfArgs {
 #ifndef RQ_LM_OF_TAPER
 #define RQ_LM_OF_TAPER 1.95
 #endif
-hipError_t rq_launch_log_metrics_of(const LogMetricsOfArgs& a, hipStream_t s);
+hipError_t rq_launch_log_metrics_of(const LogMetricsOfArgs& a, hipStream_t s, bool slim = false);
 
 // ---- competing RedQueen broadcasters against an exogenous log (rq_game.hip) ----
 struct GameArgs {

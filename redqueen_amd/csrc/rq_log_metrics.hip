@@ -38,6 +38,12 @@
 // during step 1 the stream bits][xbits][xpre].  A Cell is 16 bytes -- rank i32, tag i32,
 // and sum << 24 | count in 64 bits (ev_cap <= 2^20: count <= 2^20, sum < 2^40) -- one
 // ds_read_b128 and one ds_write_b128 per row.
+//
+// The slim entries (rq_log_metrics_slim, rq_log_metrics_of_slim) are the same body on an
+// 8-byte SlimCell (rq_log_metrics_slim_lds_bytes: up to 19,400 sinks): every kernel and every
+// step that touches a cell is a template over the cell type, CellIO<CELL> holds the two
+// layouts' load and store, and the 64-bit halves the slim cells lack live in the slot's spill
+// words behind its rows.
 #include <hip/hip_runtime.h>
 
 #include "rq_device.h"
@@ -61,26 +67,106 @@ struct __attribute__((aligned(16))) Cell {
 };
 static_assert(sizeof(Cell) == RQ_LM_CELL_BYTES, "rq_log_metrics_lds_bytes");
 
+// The slim cell.  A group with one row of the column has count 1 and sum == rank, and a cell
+// without a row count 0 and sum 0: only a column's second row in a t-group makes cs more than
+// the rank says.  So the cell keeps a bit for that case and cs itself goes to the slot's spill
+// word of the column, in the workspace.  Bits: rank -1 .. 2^20 (ev_cap <= 2^20 rows), a whole
+// i32; tm bits 0..20: tag + 1 (tag -1 .. 2^20 - 1, so 0 .. 2^20), bit 31: multi, bits 21..30
+// spare.  One ds_read_b64 and one ds_write_b64 per row.
+struct __attribute__((aligned(8))) SlimCell {
+    int rank;      // as Cell's
+    uint32_t tm;   // (tag + 1) | multi << 31
+};
+static_assert(sizeof(SlimCell) == RQ_LM_SLIM_CELL_BYTES, "rq_log_metrics_slim_lds_bytes");
+static_assert(RQ_LM_MAX_EV_CAP <= (1 << 20), "tag + 1 and the rank in 21 bits");
+constexpr uint32_t SLIM_TAG_MASK = (1u << 21) - 1u, SLIM_MULTI = 1u << 31;
+
+// What lm_play reads of a cell and writes back, for either layout: load gives the tag and
+// rank and the group's cs; store the row's new rank, tag and cs (nk rows of the group).
+template <class CELL>
+struct CellIO;
+template <>
+struct CellIO<Cell> {
+    static constexpr bool SLIM = false;
+    static __device__ __forceinline__ Cell empty()
+    {
+        Cell z;
+        z.rank = -1;
+        z.tag = -1;
+        z.cs = 0;
+        return z;
+    }
+    static __device__ __forceinline__ void load(const Cell* cell, const uint64_t*, int c, int& rank, int& tag,
+                                                uint64_t& cs)
+    {
+        const Cell s = cell[c];
+        rank = s.rank;
+        tag = s.tag;
+        cs = s.cs;
+    }
+    static __device__ __forceinline__ void store(Cell* cell, uint64_t*, int c, int rank, int tag, uint64_t cs, int)
+    {
+        Cell s;
+        s.rank = rank;
+        s.tag = tag;
+        s.cs = cs;
+        cell[c] = s;
+    }
+};
+template <>
+struct CellIO<SlimCell> {
+    static constexpr bool SLIM = true;
+    static __device__ __forceinline__ SlimCell empty()
+    {
+        SlimCell z;
+        z.rank = -1;
+        z.tm = 0u;
+        return z;
+    }
+    static __device__ __forceinline__ void load(const SlimCell* cell, const uint64_t* spill, int c, int& rank,
+                                                int& tag, uint64_t& cs)
+    {
+        const SlimCell s = cell[c];
+        rank = s.rank;
+        tag = (int)(s.tm & SLIM_TAG_MASK) - 1;
+        // one row: count 1, sum = rank; no row: 0
+        cs = tag >= 0 ? ((uint64_t)(uint32_t)s.rank << 24) | 1u : 0u;
+        if (s.tm & SLIM_MULTI) cs = spill[c];
+    }
+    static __device__ __forceinline__ void store(SlimCell* cell, uint64_t* spill, int c, int rank, int tag,
+                                                 uint64_t cs, int nk)
+    {
+        SlimCell s;
+        s.rank = rank;
+        s.tm = (uint32_t)(tag + 1) | (nk > 1 ? SLIM_MULTI : 0u);
+        cell[c] = s;
+        if (nk > 1) spill[c] = cs;
+    }
+};
+
 // rows per lane and trip of the scan (TU of wave_npsum_rows), as the fused sweep's fws_tu
 constexpr int lm_tu(int nk) { return nk == 1 ? 4 : 2; }
 
 // a block's wave: its LDS and its slot of the workspace
+template <class CELL>
 struct LmWave {
     double* scratch;
-    Cell* cell;
+    CELL* cell;
     uint32_t* sbits;   // step 1 only, in the cells' place: the stream bits, then (scope OWN) the follower bits
     uint32_t* xbits;
     uint16_t* xpre;
     double *Rt, *Rs;
     uint32_t *Rv, *Rc;
+    uint64_t* spill;   // slim cells only: cs of the columns with several rows in their last t-group
 };
 
-__device__ __forceinline__ LmWave lm_wave(const LogMetricsArgs& a, char* lds)
+template <class CELL>
+__device__ __forceinline__ LmWave<CELL> lm_wave(const LogMetricsArgs& a, char* lds)
 {
-    LmWave w;
+    LmWave<CELL> w;
     const int W = (a.log.n_sinks + 31) >> 5;
     w.scratch = reinterpret_cast<double*>(lds);
-    w.cell = reinterpret_cast<Cell*>(lds + RQ_LM_SCRATCH_BYTES);
+    w.cell = reinterpret_cast<CELL*>(lds + RQ_LM_SCRATCH_BYTES);
     w.sbits = reinterpret_cast<uint32_t*>(w.cell);
     w.xbits = reinterpret_cast<uint32_t*>(lds + RQ_LM_SCRATCH_BYTES + a.state_bytes);
     w.xpre = reinterpret_cast<uint16_t*>(w.xbits + W);
@@ -89,11 +175,13 @@ __device__ __forceinline__ LmWave lm_wave(const LogMetricsArgs& a, char* lds)
     w.Rs = w.Rt + a.log.ev_cap;
     w.Rv = reinterpret_cast<uint32_t*>(w.Rs + a.log.ev_cap);
     w.Rc = w.Rv + a.log.ev_cap;
+    w.spill = reinterpret_cast<uint64_t*>(slot + a.spill_off);
     return w;
 }
 
 // step 1, the marks: xbits = the sinks replica r's log reaches
-__device__ __forceinline__ void lm_reached(const LogView& v, int64_t r, const LmWave& w)
+template <class CELL>
+__device__ __forceinline__ void lm_reached(const LogView& v, int64_t r, const LmWave<CELL>& w)
 {
     const int lane = lane_id();
     const int NSTR = v.n_str;
@@ -137,7 +225,8 @@ __device__ __forceinline__ void lm_reached(const LogView& v, int64_t r, const Lm
 
 // scope OWN: xbits &= the followers of stream c, whose bits are built from its CSR row where
 // the stream bits were (every lane has read its words of them)
-__device__ __forceinline__ void lm_own_columns(const LogView& v, int c, const LmWave& w)
+template <class CELL>
+__device__ __forceinline__ void lm_own_columns(const LogView& v, int c, const LmWave<CELL>& w)
 {
     const int lane = lane_id();
     const int W = (v.n_sinks + 31) >> 5;
@@ -155,7 +244,8 @@ __device__ __forceinline__ void lm_own_columns(const LogView& v, int c, const Lm
 }
 
 // step 1, the index: xpre of xbits; returns S
-__device__ __forceinline__ int lm_index(const LogView& v, const LmWave& w)
+template <class CELL>
+__device__ __forceinline__ int lm_index(const LogView& v, const LmWave<CELL>& w)
 {
     const int lane = lane_id();
     const int W = (v.n_sinks + 31) >> 5;
@@ -171,15 +261,12 @@ __device__ __forceinline__ int lm_index(const LogView& v, const LmWave& w)
 }
 
 // S cells without a row (what step 1 kept in their place is dead: every lane read its words)
-__device__ __forceinline__ void lm_cells(int S, const LmWave& w)
+template <class CELL>
+__device__ __forceinline__ void lm_cells(int S, const LmWave<CELL>& w)
 {
-    for (int c = lane_id(); c < S; c += 64) {
-        Cell z;
-        z.rank = -1;
-        z.tag = -1;
-        z.cs = 0;
-        w.cell[c] = z;
-    }
+    // (slim: a cleared cell has no multi bit, so the spill words a block's earlier replicas
+    // left are never read and need no reset)
+    for (int c = lane_id(); c < S; c += 64) w.cell[c] = CellIO<CELL>::empty();
     wave_lds_sync();
 }
 
@@ -188,14 +275,16 @@ __device__ __forceinline__ void lm_cells(int S, const LmWave& w)
 // output element o.  MASKED (rq_log_metrics_of): a sink outside xbits gets no row, and an
 // event none of whose sinks is a column is no event -- it opens no t-group and is not counted
 // (xbits of rq_log_metrics holds every sink of every event, so there nothing is masked).
-template <int NK, bool MASKED>
+template <int NK, bool MASKED, class CELL>
 __device__ __forceinline__ void lm_play(const LogMetricsArgs& a, const LogView& log, int64_t r, int64_t o, int S,
-                                        const LmWave& w, const int64_t (&km1)[NK])
+                                        const LmWave<CELL>& w, const int64_t (&km1)[NK])
 {
+    using IO = CellIO<CELL>;
     constexpr int NV = NK + 2;
     const int lane = lane_id();
     double* scratch = w.scratch;
-    Cell* cell = w.cell;
+    CELL* cell = w.cell;
+    uint64_t* spill = w.spill;
     const uint32_t* xbits = w.xbits;
     const uint16_t* xpre = w.xpre;
     double *Rt = w.Rt, *Rs = w.Rs;
@@ -231,9 +320,10 @@ __device__ __forceinline__ void lm_play(const LogMetricsArgs& a, const LogView& 
             double o1[1];
             wave_npsum<1>((int64_t)S,
                           [&](int64_t k, double* v) {
-                              const Cell c = cell[k];
-                              v[0] = c.tag >= 0 ? (double)(int64_t)(c.cs >> 24) / (double)(int)(c.cs & 0xFFFFFFu)
-                                                : 0.0;
+                              int rk, tg;
+                              uint64_t cs;
+                              IO::load(cell, spill, (int)k, rk, tg, cs);
+                              v[0] = tg >= 0 ? (double)(int64_t)(cs >> 24) / (double)(int)(cs & 0xFFFFFFu) : 0.0;
                           },
                           scratch, o1);
             rowsum = o1[0];
@@ -262,6 +352,7 @@ __device__ __forceinline__ void lm_play(const LogMetricsArgs& a, const LogView& 
 
     log_walk(log, r, [&](double t, bool own, int p0, int p1, int xfirst) {
         bool opened = !MASKED;
+        bool spilled = false;   // slim: a spill word was stored in this event
         if (!MASKED) open(t, own);
         for (int e = p0; e < p1; e += 64) {
             bool act = e + lane < p1;
@@ -285,20 +376,22 @@ __device__ __forceinline__ void lm_play(const LogMetricsArgs& a, const LogView& 
             }
             if (act) {
                 const int c = xp + __popc(wb & ((1u << (x & 31)) - 1u));
-                Cell s = cell[c];
-                ov = s.tag >= 0;
-                same = s.tag == gid;
-                k = (int)(s.cs & 0xFFFFFFu);
-                sm = (int64_t)(s.cs >> 24);
-                const int rn = next_rank(own, s.rank);
+                int rk, tg;
+                uint64_t cs;
+                IO::load(cell, spill, c, rk, tg, cs);
+                ov = tg >= 0;
+                same = tg == gid;
+                k = (int)(cs & 0xFFFFFFu);
+                sm = (int64_t)(cs >> 24);
+                const int rn = next_rank(own, rk);
                 nk = same ? k + 1 : 1;
                 ns = same ? sm + rn : (int64_t)rn;
-                s.rank = rn;
-                s.tag = gid;
-                s.cs = ((uint64_t)ns << 24) | (uint32_t)nk;
-                cell[c] = s;
+                IO::store(cell, spill, c, rn, gid, ((uint64_t)ns << 24) | (uint32_t)nk, nk);
             }
-            if (__ballot(same)) tie = true;
+            if (__ballot(same)) {   // same: nk > 1, the rows that store a spill word
+                tie = true;
+                spilled = true;
+            }
             nvalid += popc(__ballot(act && !ov));
             // the old cell sm / k and the new one ns / nk
             const uint64_t means = __ballot(act && (nk > 1 || k > 1));
@@ -330,6 +423,15 @@ __device__ __forceinline__ void lm_play(const LogMetricsArgs& a, const LogView& 
             }
         }
         wave_lds_sync();
+        if (IO::SLIM && spilled) {
+            // a spill word is loaded by whichever lane the column's next row falls on, in a
+            // later event or in emit's sum: drain the stores and order them before those
+            // loads at workgroup scope (same wave, same CU), as step 3 does for the rows.
+            // The sinks of one row are distinct, so within the event nothing is re-read.
+            __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        }
     });
     if (have) emit();
     {   // the staged rows of the last, partial store
@@ -365,11 +467,11 @@ __device__ __forceinline__ void lm_play(const LogMetricsArgs& a, const LogView& 
     wave_lds_sync();   // the scan's scratch and the cells before the next marks
 }
 
-template <int NK>
+template <int NK, class CELL>
 __global__ __launch_bounds__(64) void rq_log_metrics_k(LogMetricsArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char lds_lm[];
-    const LmWave w = lm_wave(a, lds_lm);
+    const LmWave<CELL> w = lm_wave<CELL>(a, lds_lm);
     int64_t km1[NK];
 #pragma unroll
     for (int q = 0; q < NK; ++q) km1[q] = (int64_t)a.Ks[q] - 1;
@@ -401,12 +503,12 @@ __device__ __forceinline__ int64_t of_first_item(int64_t n, unsigned b, unsigned
 // each replica it meets a run of consecutive tracked sources, played one after the other in
 // the block's slot.  Scope DF: the columns are the replica's, found once per run.  Scope OWN:
 // they are masked with the tracked source's followers, found again per source.
-template <int NK>
+template <int NK, class CELL>
 __global__ __launch_bounds__(64) void rq_log_metrics_of_k(LogMetricsOfArgs b)
 {
     extern __shared__ __attribute__((aligned(16))) char lds_lm[];
     const LogMetricsArgs& a = b.m;
-    const LmWave w = lm_wave(a, lds_lm);
+    const LmWave<CELL> w = lm_wave<CELL>(a, lds_lm);
     int64_t km1[NK];
 #pragma unroll
     for (int q = 0; q < NK; ++q) km1[q] = (int64_t)a.Ks[q] - 1;
@@ -432,46 +534,66 @@ __global__ __launch_bounds__(64) void rq_log_metrics_of_k(LogMetricsOfArgs b)
     }
 }
 
-template <int NK>
+// the block's LDS: the cells' layout is the one the host sized state_bytes for
+template <class CELL>
+size_t lm_lds_bytes(const LogMetricsArgs& a)
+{
+    return CellIO<CELL>::SLIM ? rq_log_metrics_slim_lds_bytes(a.log.n_sinks, a.log.n_str)
+                              : rq_log_metrics_lds_bytes(a.log.n_sinks, a.log.n_str);
+}
+
+template <int NK, class CELL>
 hipError_t launch_nk(const LogMetricsArgs& a, hipStream_t s)
 {
-    const size_t lds = rq_log_metrics_lds_bytes(a.log.n_sinks, a.log.n_str);
-    hipLaunchKernelGGL((rq_log_metrics_k<NK>), dim3((unsigned)a.n_slots), dim3(64), lds, s, a);
+    const size_t lds = lm_lds_bytes<CELL>(a);
+    hipLaunchKernelGGL((rq_log_metrics_k<NK, CELL>), dim3((unsigned)a.n_slots), dim3(64), lds, s, a);
     return hipGetLastError();
 }
 
-template <int NK>
+template <int NK, class CELL>
 hipError_t launch_of_nk(LogMetricsOfArgs b, hipStream_t s)
 {
-    const size_t lds = rq_log_metrics_lds_bytes(b.m.log.n_sinks, b.m.log.n_str);
+    const size_t lds = lm_lds_bytes<CELL>(b.m);
     // tapered shares only when the blocks run in several rounds: with every block resident
     // the longest block is the launch's time
-    const int64_t resident = (int64_t)rq_occupancy(rq_log_metrics_of_k<NK>, 64, lds) * rq_cu_count();
+    const int64_t resident = (int64_t)rq_occupancy(rq_log_metrics_of_k<NK, CELL>, 64, lds) * rq_cu_count();
     b.taper = resident > 0 && b.m.n_slots > resident ? RQ_LM_OF_TAPER : 1.0;
-    hipLaunchKernelGGL((rq_log_metrics_of_k<NK>), dim3((unsigned)b.m.n_slots), dim3(64), lds, s, b);
+    hipLaunchKernelGGL((rq_log_metrics_of_k<NK, CELL>), dim3((unsigned)b.m.n_slots), dim3(64), lds, s, b);
     return hipGetLastError();
+}
+
+template <class CELL>
+hipError_t launch_cells(const LogMetricsArgs& a, hipStream_t s)
+{
+    switch (a.nK) {
+    case 1: return launch_nk<1, CELL>(a, s);
+    case 2: return launch_nk<2, CELL>(a, s);
+    case 3: return launch_nk<3, CELL>(a, s);
+    case 4: return launch_nk<4, CELL>(a, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+template <class CELL>
+hipError_t launch_of_cells(const LogMetricsOfArgs& b, hipStream_t s)
+{
+    switch (b.m.nK) {
+    case 1: return launch_of_nk<1, CELL>(b, s);
+    case 2: return launch_of_nk<2, CELL>(b, s);
+    case 3: return launch_of_nk<3, CELL>(b, s);
+    case 4: return launch_of_nk<4, CELL>(b, s);
+    }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace
 
-hipError_t rq_launch_log_metrics(const LogMetricsArgs& a, hipStream_t s)
+hipError_t rq_launch_log_metrics(const LogMetricsArgs& a, hipStream_t s, bool slim)
 {
-    switch (a.nK) {
-    case 1: return launch_nk<1>(a, s);
-    case 2: return launch_nk<2>(a, s);
-    case 3: return launch_nk<3>(a, s);
-    case 4: return launch_nk<4>(a, s);
-    }
-    return hipErrorInvalidValue;
+    return slim ? launch_cells<SlimCell>(a, s) : launch_cells<Cell>(a, s);
 }
 
-hipError_t rq_launch_log_metrics_of(const LogMetricsOfArgs& b, hipStream_t s)
+hipError_t rq_launch_log_metrics_of(const LogMetricsOfArgs& b, hipStream_t s, bool slim)
 {
-    switch (b.m.nK) {
-    case 1: return launch_of_nk<1>(b, s);
-    case 2: return launch_of_nk<2>(b, s);
-    case 3: return launch_of_nk<3>(b, s);
-    case 4: return launch_of_nk<4>(b, s);
-    }
-    return hipErrorInvalidValue;
+    return slim ? launch_of_cells<SlimCell>(b, s) : launch_of_cells<Cell>(b, s);
 }

@@ -375,6 +375,12 @@ class Graph:
     # it refuses takes the other route), "replay" = rq_log_expand + rq_metrics_replay_batch; the
     # same bits, C3 with 10,000 replicas in 45-52 ms against 3,053-3,920 ms (profiles/game_c3_logmetrics.json)
     GAME_METRICS = "log"
+    # whether "log" may take rq_log_metrics_slim where rq_log_metrics refuses the graph (more than
+    # LOG_METRICS_MAX_SINKS sinks) instead of the replay route: C5's graph with end_time 10 and 64
+    # replicas in 25.2-25.5 ms against 209.0-215.7 ms, the same bits (profiles/log_metrics_slim.json,
+    # DESIGN section 33)
+    GAME_METRICS_SLIM = True
+    game_metrics_route = None    # the route stage 3 of the last game took: "log", "log-slim" or "replay"
 
     def _game_launch(self, players, seeds, ev_t, ev_src, counts, max_events, out_cap, use):
         """One rq_log_game: ``players`` [(src_id, q, s array)], ``seeds`` device int32
@@ -421,8 +427,11 @@ class Graph:
         by ``ctrl_seed``); rq_log_game plays the Opts against that log, one launch per grid
         point; metrics and counts come from the completed log, pandas-exact on the
         start-time ties every game has: by rq_log_metrics (``GAME_METRICS`` "log"; a graph or
-        a log capacity above 2^20 events, which it refuses, takes the other route) or by
-        rq_log_expand + rq_metrics_replay_batch ("replay"), the same bits.  With ``check`` replicas whose output log overflowed are rerun at doubled capacity
+        a log capacity above 2^20 events, which it refuses, takes the other route -- with
+        ``GAME_METRICS_SLIM``, a graph of up to LOG_METRICS_SLIM_MAX_SINKS sinks goes to
+        rq_log_metrics_slim instead) or by rq_log_expand + rq_metrics_replay_batch ("replay"),
+        the same bits; ``self.game_metrics_route`` names the route taken ("log", "log-slim",
+        "replay").  With ``check`` replicas whose output log overflowed are rerun at doubled capacity
         (``self.reruns``).  The result carries ``player_posts`` [R, P] and ``player_ids``.
         With ``self.game_timing`` set, ``self.game_ms`` holds the device milliseconds of the
         three stages (exogenous pass, game launches and reruns, and under the key "replay"
@@ -551,10 +560,12 @@ class Graph:
         lm = None
         if self.GAME_METRICS == "log":   # straight from the log, where graph and capacity are supported
             try:
-                lm = BatchResult(self, None, out_counts, None, out_t, out_src, Ks, n_grid, n_rep)._log_metrics(Ks, use)
+                lm = BatchResult(self, None, out_counts, None, out_t, out_src, Ks, n_grid, n_rep)._log_metrics(
+                    Ks, use, None if self.GAME_METRICS_SLIM else False)
             except L.RQError as e:
                 if e.code != L.RQ_EUNSUPPORTED:
                     raise
+        self.game_metrics_route = "replay" if lm is None else ("log-slim" if lm.slim else "log")
         lo = 0
         if lm is not None:
             metrics.copy_(lm.metrics)
@@ -1113,26 +1124,56 @@ class BatchResult:
 
     LOG_METRICS_WS_BYTES = 1 << 31   # workspace budget of one rq_log_metrics call
 
-    def log_metrics(self, Ks=None, stream=None):
+    def _lm_entry(self, slim, nK, of=False):
+        """(name, workspace query, entry, slim) of log_metrics' / source_metrics' ABI entry.
+        ``slim`` False: the 16-byte cells; True: the 8-byte cells (rq_log_metrics_slim,
+        rq_log_metrics_of_slim); None: the 16-byte entry, and the slim one where the 16-byte
+        one answers RQ_EUNSUPPORTED and the slim one does not."""
+        lib = L.lib()
+        base = "rq_log_metrics_of" if of else "rq_log_metrics"
+        plain = (base, getattr(lib, base + "_workspace"), getattr(lib, base), False)
+        if slim is False:
+            return plain
+        if not all(L.has(fn) for fn in L.OPTIONAL_SLIM):
+            if slim:
+                raise L.RQError(base + "_slim", L.RQ_EUNSUPPORTED)
+            return plain
+        thin = (base + "_slim", getattr(lib, base + "_slim_workspace"), getattr(lib, base + "_slim"), True)
+        if slim:
+            return thin
+        R, cap = self.ev_t.shape
+        nb = C.c_size_t()
+        args = (self.graph._h,) + ((1,) if of else ()) + (max(1, R), max(1, cap), nK, C.byref(nb))
+        if plain[1](*args) == L.RQ_EUNSUPPORTED and thin[1](*args) == L.RQ_OK:
+            return thin
+        return plain
+
+    def log_metrics(self, Ks=None, stream=None, slim=None):
         """The whole-horizon metrics and counts straight from the event logs, exact on
         equal times (rq_log_metrics): what rq_metrics_replay_batch gives on the logs'
         dataframe rows, bit for bit, without a dataframe.  ``Ks``: default the result's
         own.  Returns a ``LogMetrics`` of device tensors: ``metrics`` [R, nK + 2],
         ``counts`` [R, 4] (own events, other events, pivot rows, pivot columns) and
         ``status`` [R] (ST_TIE is informational, ST_EMPTY replicas are NaN).  Replicas go
-        in chunks that keep the workspace within LOG_METRICS_WS_BYTES.  Raises
-        RQError(RQ_EUNSUPPORTED) for a graph with duplicate edges or more than
-        LOG_METRICS_MAX_SINKS sinks, and for logs with room for more than 2^20 events per
+        in chunks that keep the workspace within LOG_METRICS_WS_BYTES.  ``slim``: the cell
+        layout.  None (default): rq_log_metrics, and rq_log_metrics_slim -- 8-byte cells,
+        the same bits, a larger workspace -- for the graphs only the latter takes (more
+        than LOG_METRICS_MAX_SINKS and up to LOG_METRICS_SLIM_MAX_SINKS sinks); False /
+        True: that entry, whatever the graph (``.slim`` of the result says which ran).
+        Raises RQError(RQ_EUNSUPPORTED) for a graph with duplicate edges or more sinks than
+        the entry takes, and for logs with room for more than 2^20 events per
         replica (``ev_t.shape[1]``; ``utils.replay_columns`` over ``log_columns()`` takes
         those); needs event_log=True."""
         self._log_graph()
         ks = self._log_ks(Ks)
         use = stream or torch.cuda.current_stream()
         with torch.cuda.stream(use):
-            return self._log_metrics(ks, use)
+            return self._log_metrics(ks, use, slim)
 
-    def _log_metrics(self, ks, use):
-        g, lib = self.graph, L.lib()
+    def _log_metrics(self, ks, use, slim=None):
+        g = self.graph
+        name, query, entry, thin = self._lm_entry(slim, ks.size)
+        wname = name + "_workspace"
         dev = self.ev_t.device
         R, cap = self.ev_t.shape
         metrics = torch.empty((R, ks.size + 2), dtype=torch.float64, device=dev)
@@ -1140,31 +1181,30 @@ class BatchResult:
         status = torch.empty(R, dtype=torch.int32, device=dev)
         nb = C.c_size_t()
         if R == 0 or cap == 0:   # nothing to play: every replica is empty
-            L.check("rq_log_metrics_workspace", lib.rq_log_metrics_workspace(g._h, 1, 1, ks.size, C.byref(nb)))
+            L.check(wname, query(g._h, 1, 1, ks.size, C.byref(nb)))
             metrics.fill_(float("nan"))
             counts.zero_()
             status.fill_(L.ST_EMPTY)
-            return LogMetrics([int(k) for k in ks], metrics, counts, status)
+            return LogMetrics([int(k) for k in ks], metrics, counts, status, thin)
         # the whole batch in one launch if its workspace (which stops growing at a fixed
         # number of blocks) fits the budget, else as many replicas a call as fit it
         chunk = R
-        L.check("rq_log_metrics_workspace", lib.rq_log_metrics_workspace(g._h, R, cap, ks.size, C.byref(nb)))
+        L.check(wname, query(g._h, R, cap, ks.size, C.byref(nb)))
         if nb.value > self.LOG_METRICS_WS_BYTES:
-            L.check("rq_log_metrics_workspace", lib.rq_log_metrics_workspace(g._h, 1, cap, ks.size, C.byref(nb)))
+            L.check(wname, query(g._h, 1, cap, ks.size, C.byref(nb)))
             chunk = max(1, min(R, self.LOG_METRICS_WS_BYTES // nb.value))
-            L.check("rq_log_metrics_workspace",
-                    lib.rq_log_metrics_workspace(g._h, chunk, cap, ks.size, C.byref(nb)))
+            L.check(wname, query(g._h, chunk, cap, ks.size, C.byref(nb)))
         ws = torch.empty(max(256, nb.value), dtype=torch.uint8, device=dev)
         for lo in range(0, R, chunk):
             n = min(chunk, R - lo)
-            L.check("rq_log_metrics", lib.rq_log_metrics(
+            L.check(name, entry(
                 g._h, self.ev_t[lo:].data_ptr(), self.ev_src[lo:].data_ptr(), self.counts[lo:].data_ptr(),
                 n, cap, ks.ctypes.data_as(L._pi32), ks.size, metrics[lo:].data_ptr(),
                 counts[lo:].data_ptr(), status[lo:].data_ptr(), ws.data_ptr(), ws.numel(),
                 use.cuda_stream))   # ws: allocated on `use`, reused there only
-        return LogMetrics([int(k) for k in ks], metrics, counts, status)
+        return LogMetrics([int(k) for k in ks], metrics, counts, status, thin)
 
-    def source_metrics(self, src_ids=None, scope="own", Ks=None, stream=None):
+    def source_metrics(self, src_ids=None, scope="own", Ks=None, stream=None, slim=None):
         """log_metrics for any sources of the graph (rq_log_metrics_of): the reference's
         time_in_top_k(df, K, src_id=c), average_rank(df, src_id=c) and int_r_2 for every
         c of ``src_ids`` -- default the result's ``player_ids`` when it has them, else
@@ -1173,8 +1213,9 @@ class BatchResult:
         on.  Returns a ``SourceMetrics`` of device tensors: ``metrics`` [R, P, nK + 2],
         ``counts`` [R, P, 4] (c's events with a row, the others', pivot rows, pivot
         columns) and ``status`` [R, P].  Sources go in chunks of LOG_OF_MAX_SRC, replicas
-        in chunks that keep the workspace within LOG_METRICS_WS_BYTES.  Raises as
-        log_metrics does; needs event_log=True."""
+        in chunks that keep the workspace within LOG_METRICS_WS_BYTES.  ``slim``: as
+        log_metrics' (rq_log_metrics_of_slim).  Raises as log_metrics does; needs
+        event_log=True."""
         g = self._log_graph()
         ks = self._log_ks(Ks)
         if scope not in ("df", "own"):
@@ -1189,10 +1230,12 @@ class BatchResult:
             raise L.RQError("rq_log_metrics_of", L.RQ_EUNSUPPORTED)
         use = stream or torch.cuda.current_stream()
         with torch.cuda.stream(use):
-            return self._source_metrics(ids, L.LOG_OF_OWN if scope == "own" else L.LOG_OF_DF, ks, use)
+            return self._source_metrics(ids, L.LOG_OF_OWN if scope == "own" else L.LOG_OF_DF, ks, use, slim)
 
-    def _source_metrics(self, ids, scope, ks, use):
-        g, lib = self.graph, L.lib()
+    def _source_metrics(self, ids, scope, ks, use, slim=None):
+        g = self.graph
+        name, query, entry, thin = self._lm_entry(slim, ks.size, of=True)
+        wname = name + "_workspace"
         dev = self.ev_t.device
         R, cap = self.ev_t.shape
         P, nK = ids.size, ks.size
@@ -1200,9 +1243,9 @@ class BatchResult:
         out = SourceMetrics([int(s) for s in ids], [int(k) for k in ks],
                             torch.empty((R, P, nK + 2), dtype=torch.float64, device=dev),
                             torch.empty((R, P, 4), dtype=torch.int64, device=dev),
-                            torch.empty((R, P), dtype=torch.int32, device=dev))
+                            torch.empty((R, P), dtype=torch.int32, device=dev), thin)
         if R == 0 or cap == 0:   # nothing to play: every (replica, source) is empty
-            L.check("rq_log_metrics_of_workspace", lib.rq_log_metrics_of_workspace(g._h, 1, 1, 1, nK, C.byref(nb)))
+            L.check(wname, query(g._h, 1, 1, 1, nK, C.byref(nb)))
             out.metrics.fill_(float("nan"))
             out.counts.zero_()
             out.status.fill_(L.ST_EMPTY)
@@ -1214,14 +1257,11 @@ class BatchResult:
             # the whole batch in one launch if its workspace (which stops growing at a fixed
             # number of blocks) fits the budget, else as many replicas a call as fit it
             chunk = R
-            L.check("rq_log_metrics_of_workspace",
-                    lib.rq_log_metrics_of_workspace(g._h, n_src, R, cap, nK, C.byref(nb)))
+            L.check(wname, query(g._h, n_src, R, cap, nK, C.byref(nb)))
             if nb.value > self.LOG_METRICS_WS_BYTES:
-                L.check("rq_log_metrics_of_workspace",
-                        lib.rq_log_metrics_of_workspace(g._h, 1, 1, cap, nK, C.byref(nb)))
+                L.check(wname, query(g._h, 1, 1, cap, nK, C.byref(nb)))
                 chunk = max(1, min(R, self.LOG_METRICS_WS_BYTES // nb.value // n_src))
-                L.check("rq_log_metrics_of_workspace",
-                        lib.rq_log_metrics_of_workspace(g._h, n_src, chunk, cap, nK, C.byref(nb)))
+                L.check(wname, query(g._h, n_src, chunk, cap, nK, C.byref(nb)))
             if ws is None or ws.numel() < nb.value:
                 ws = torch.empty(max(256, nb.value), dtype=torch.uint8, device=dev)
             whole = n_src == P
@@ -1232,7 +1272,7 @@ class BatchResult:
                            (torch.empty((n, n_src, nK + 2), dtype=torch.float64, device=dev),
                             torch.empty((n, n_src, 4), dtype=torch.int64, device=dev),
                             torch.empty((n, n_src), dtype=torch.int32, device=dev)))
-                L.check("rq_log_metrics_of", lib.rq_log_metrics_of(
+                L.check(name, entry(
                     g._h, sub.ctypes.data_as(L._pi64), n_src, scope, self.ev_t[lo:].data_ptr(),
                     self.ev_src[lo:].data_ptr(), self.counts[lo:].data_ptr(), n, cap,
                     ks.ctypes.data_as(L._pi32), nK, m.data_ptr(), c.data_ptr(), s.data_ptr(),
@@ -1243,14 +1283,15 @@ class BatchResult:
                     out.status[lo:lo + n, p0:p0 + n_src] = s
         return out
 
-    def player_metrics(self, scope="own", Ks=None, stream=None):
+    def player_metrics(self, scope="own", Ks=None, stream=None, slim=None):
         """source_metrics of the game's players (``player_ids``, in their order): how
         visible every competing Opt ended up, on its own followers' feeds (scope "own") or
-        on the whole dataframe ("df").  ValueError for a result without players."""
+        on the whole dataframe ("df"); ``slim`` as source_metrics'.  ValueError for a
+        result without players."""
         ids = getattr(self, "player_ids", None)
         if not ids:
             raise ValueError("player_metrics: the result of a game (Opt broadcasters among the sources) expected")
-        return self.source_metrics(ids, scope=scope, Ks=Ks, stream=stream)
+        return self.source_metrics(ids, scope=scope, Ks=Ks, stream=stream, slim=slim)
 
     def events(self, i):
         """(t, src_id) numpy arrays of replica i (needs event_log=True)."""
@@ -1264,10 +1305,10 @@ class LogMetrics:
     """BatchResult.log_metrics' outputs: ``metrics`` [R, nK + 2] (top_K..., avg_rank,
     r_2), ``counts`` [R, 4] (the controlled source's events with an edge, the others',
     pivot rows, pivot columns) and ``status`` [R] (0, ST_TIE: informational, or ST_EMPTY:
-    metrics NaN), device tensors."""
+    metrics NaN), device tensors; ``slim``: the 8-byte-cell entry computed them."""
 
-    def __init__(self, Ks, metrics, counts, status):
-        self.Ks, self.metrics, self.counts, self.status = Ks, metrics, counts, status
+    def __init__(self, Ks, metrics, counts, status, slim=False):
+        self.Ks, self.metrics, self.counts, self.status, self.slim = Ks, metrics, counts, status, slim
 
     def top_k(self, k):
         return self.metrics[:, self.Ks.index(k)]
@@ -1285,10 +1326,11 @@ class SourceMetrics:
     """BatchResult.source_metrics' outputs for the sources ``src_ids`` [P]: ``metrics``
     [R, P, nK + 2] (top_K..., avg_rank, r_2), ``counts`` [R, P, 4] (the source's events
     with a row, the other sources', pivot rows, pivot columns) and ``status`` [R, P] (0,
-    ST_TIE: informational, or ST_EMPTY: metrics NaN), device tensors."""
+    ST_TIE: informational, or ST_EMPTY: metrics NaN), device tensors; ``slim``: the
+    8-byte-cell entry computed them."""
 
-    def __init__(self, src_ids, Ks, metrics, counts, status):
-        self.src_ids, self.Ks = src_ids, Ks
+    def __init__(self, src_ids, Ks, metrics, counts, status, slim=False):
+        self.src_ids, self.Ks, self.slim = src_ids, Ks, slim
         self.metrics, self.counts, self.status = metrics, counts, status
 
     def top_k(self, k):
