@@ -301,7 +301,10 @@ int rq_plan_info(rq_graph_t g, const rq_batch_desc* b, int64_t* info);
  * without event log or max_events, RQ_SWEEP_SCAN=0 in the environment turns it off) or the
  * scan kernel runs after the sweep (0); [9] the merged fused sweep on K=1 sink bitsets
  * counts a tile's top-1 sets with its events blocked four to a lane (1; graphs of at least
- * 385 sinks, RQ_PHASEC_BLK=0 in the environment turns it off) or one event per lane (0).
+ * 385 sinks, RQ_PHASEC_BLK=0 in the environment turns it off) or one event per lane (0);
+ * [10] the sweep of [8] keeps a replica's pivot rows as 16-byte records (1; one K, at most
+ * 65535 sinks and sinks x merged entries per replica below 2^32, RQ_ROWS_PACKED=0 in the
+ * environment turns it off) or in four arrays (0).
  * Entries past the last defined one are not written. */
 int rq_plan_info_n(rq_graph_t g, const rq_batch_desc* b, int64_t* info, int n);
 

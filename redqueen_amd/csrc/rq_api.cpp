@@ -668,13 +668,14 @@ int rq_plan_info(rq_graph_t g, const rq_batch_desc* b, int64_t* info)
 int rq_plan_info_n(rq_graph_t g, const rq_batch_desc* b, int64_t* out, int n)
 {
     if (!out || n < 0) return RQ_EINVAL;
-    int64_t info[10];
+    int64_t info[11];
     Plan p;
     const int rc = plan_call(g, b, rqh::read_knobs(), 0.0, &p);
     if (rc) return rc;
     rqh::plan_info(p, b->ctrl_kind, info);
     info[9] = p.blk ? 1 : 0;
-    std::copy(info, info + std::min(n, 10), out);
+    info[10] = p.rows16 ? 1 : 0;
+    std::copy(info, info + std::min(n, 11), out);
     return RQ_OK;
 }
 
@@ -734,7 +735,9 @@ int rq_run_batch(rq_graph_t g, const rq_batch_desc* b, const rq_outputs* out, vo
         {
             TimedLaunch tl(K_SWEEP, s);
             const SweepInst inst = rqh::sweep_inst(p, b->ctrl_kind);
-            const hipError_t e = inst.fused ? rq_launch_sweep_fw(sa, inst, s) : rq_launch_sweep(sa, inst, s);
+            // 16-byte rows (inst.pk) take the bytes of rows_t and rows_sum, back to back
+            const hipError_t e = inst.fused ? rq_launch_sweep_fw(sa, inst, s, p.off_rv - p.off_rt)
+                                            : rq_launch_sweep(sa, inst, s);
             if (e != hipSuccess) return RQ_EHIP;
         }
         // scan

@@ -48,6 +48,8 @@ struct SweepInst {
                   //   sums, written to SweepArgs.metrics; no rq_scan launch for the chunk)
     bool blk;     // fused, mrg, bits: phase C with the tile's events blocked four to a lane
                   //   (BlkFlags) once every sink has a row, else one event per lane throughout
+    bool pk;      // fused, mrg, scan, nK == 1: the replica's pivot rows as 16-byte records {t, sumR u32,
+                  //   cnt u16, valid u16} in the bytes of rows_t / rows_sum, else the four row arrays
 };
 // SweepInst.blk: lane 16 b + g scans events 4g .. 4g + 3 over the RQ_BLK_CB words of column
 // block b.  An even number of words per block (two columns per trip, 8-byte reads), so the
@@ -91,6 +93,16 @@ namespace rqh {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// SweepInst.pk: whether a 16-byte row record holds every row of a replica.  One K; valid and
+// cnt count sinks (16 bits each); sumR, the sum of the sinks' ranks, grows by at most n_sinks per
+// wall event and a replica plays at most mrg_stride merged entries (32 bits).
+inline bool rows16_fits(int nK, int n_sinks, int64_t mrg_stride)
+{
+    // both factors bounded first: the product stays below 2^48, no wrap
+    return nK == 1 && n_sinks >= 0 && n_sinks <= 65535 && mrg_stride >= 0 && mrg_stride < ((int64_t)1 << 32) &&
+           (uint64_t)n_sinks * (uint64_t)mrg_stride < ((uint64_t)1 << 32);
+}
+
 // sink tiles of a graph of n_sinks sinks, and the workspace of rq_log_followers_tiled on it:
 // one int32 flag per (replica, tile), rounded up to 256 bytes
 inline int followers_tiles(int n_sinks) { return (n_sinks + RQ_FOLLOWERS_TILE_SINKS - 1) / RQ_FOLLOWERS_TILE_SINKS; }
@@ -133,6 +145,9 @@ struct Knobs {
     bool ctrl_draws = true;
     // RQ_SWEEP_SCAN=0: the scan kernel instead of the sweep's own scan; A/B, test_gpu_sweep_scan
     bool sweep_scan = true;
+    // RQ_ROWS_PACKED=0: the scanning merged fused sweep keeps its rows in the four row arrays
+    // instead of 16-byte records; A/B, test_gpu_rows_packed
+    bool rows_packed = true;
     // RQ_GEN_SPLIT=0: rq_gen_streams for every stream instead of rq_gen_classes' body per
     // class of source kinds; A/B, test_gpu_gen_split
     bool gen_split = true;
@@ -283,6 +298,10 @@ struct Plan {
     // fwm without event log or max_events: each wave integrates the rows of the replica it
     // swept (SweepInst.scan), the chunk launches no rq_scan; RQ_SWEEP_SCAN=0 keeps the kernel
     bool scan = false;
+    // scan at one K where a 16-byte record holds every row (rows16_fits with this plan's
+    // mrg_stride, so a rerun with doubled capacities decides again): the sweep writes and reads
+    // records in the bytes of off_rt .. off_rv (SweepInst.pk); RQ_ROWS_PACKED=0 keeps the arrays
+    bool rows16 = false;
     // fwm on sink bits with at least RQ_BLK_MIN_NW words: phase C event-blocked (SweepInst.blk),
     // mask rows of RQ_BLK_MSTRIDE words; RQ_PHASEC_BLK=0 keeps the word loop and its stride
     bool blk = false;

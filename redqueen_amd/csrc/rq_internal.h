@@ -221,8 +221,9 @@ hipError_t rq_launch_merge_groups(const MergeArgs& a, hipStream_t s);
 hipError_t rq_launch_merge_sub(const MergeArgs& a, hipStream_t s);
 // longest-first order of n <= 65536 replicas by len (descending; ties in any order)
 hipError_t rq_launch_order(const int* len, int64_t n, int* order, hipStream_t s);
-// the fused pair of rq_launch_sweep (SweepInst.fused)
-hipError_t rq_launch_sweep_fw(const SweepArgs& a, const SweepInst& i, hipStream_t s);
+// the fused pair of rq_launch_sweep (SweepInst.fused); rows16_bytes: what the caller has at
+// a.rows_t for the 16-byte row records of a SweepInst.pk instance
+hipError_t rq_launch_sweep_fw(const SweepArgs& a, const SweepInst& i, hipStream_t s, size_t rows16_bytes = 0);
 
 // Blocks per CU a kernel reaches at `threads` threads and `lds` bytes of dynamic LDS
 // (the runtime's occupancy: VGPR, SGPR and LDS limits), cached per (kernel, threads,

@@ -24,6 +24,7 @@ Knobs read_knobs()
     if (const char* e = getenv("RQ_FWM")) k.fwm = atoi(e) != 0;
     if (const char* e = getenv("RQ_CTRL_DRAWS")) k.ctrl_draws = atoi(e) != 0;
     if (const char* e = getenv("RQ_SWEEP_SCAN")) k.sweep_scan = atoi(e) != 0;
+    if (const char* e = getenv("RQ_ROWS_PACKED")) k.rows_packed = atoi(e) != 0;
     if (const char* e = getenv("RQ_GEN_SPLIT")) k.gen_split = atoi(e) != 0;
     if (const char* e = getenv("RQ_PHASEC_BLK")) k.phasec_blk = atoi(e) != 0;
     if (const char* e = getenv("RQ_FW_W")) k.fw_w = atoi(e);
@@ -115,6 +116,7 @@ SweepInst sweep_inst(const Plan& p, int ctrl_kind, bool fused, int W, bool col16
     i.pair = fused && i.mrg && p.pair;
     i.scan = fused && i.mrg && p.scan;
     i.blk = fused && i.mrg && p.blk;
+    i.pk = i.scan && p.rows16;
     return i;
 }
 int sweep_blocks_per_cu(const SweepInst& i, int wpb, size_t lds)
@@ -437,6 +439,10 @@ void plan_fused_lds(const GraphTopo* g, const rq_batch_desc* b, const Knobs& kn,
     }
     if (!p->fw) p->fwm = false;
     if (!p->fwm) p->pair = p->scan = p->blk = false;
+    // the sweep's own rows as 16-byte records; the occupancy searches above score the array
+    // instance (the records change no LDS byte and the instance is not heavier in registers)
+    p->rows16 = p->scan && rows16_fits(p->nK, g->n_sinks, p->mrg_stride);
+    p->rows16 = p->rows16 && kn.rows_packed;   // A/B and tests
     if (p->blk) p->mstride = mstride;
     if (p->fw) p->mrg = p->fwm;   // the merge kernel feeds the fused sweep too
 }

@@ -350,7 +350,9 @@ struct AggX {
 // Pivot rows.  LOG sweep: lane (row - s0) stages a row until 64 are staged,
 // then one coalesced store per field.  The fast sweep stores whole tiles
 // itself and only keeps nrow / last_t here (s0 == nrow).
-template <int NK>
+// PK (the merged fused sweep's own rows, K = 1, read back by the wave that wrote them): a row
+// is one 16-byte record instead of an entry of four arrays (RowStage<NK, true> below).
+template <int NK, bool PK = false>
 struct RowStage {
     double r_t, r_sum;
     int r_valid;
@@ -441,6 +443,44 @@ struct RowStage {
         const int rem = (int)(nrow - s0);
         if (lane < rem) store(s0 + lane);
         s0 = nrow;
+    }
+};
+
+// A K = 1 pivot row as one 16-byte record {t : f64, sumR : u32, cnt | valid << 16 : u32}.  sumR
+// is the exact integer rank sum (the planner admits the layout only where n_sinks x the
+// replica's merged entries stays below 2^32), cnt and valid are at most n_sinks <= 65535.
+// One address and one 16-byte store per row; rq::scan_rows16 reads a record back with one
+// 16-byte load.  Only what the merged fused sweep uses of RowStage: no staged rows, and no
+// pending slots either -- with one store a row the rows go out at the end of their tile
+// (place_rows), which measured faster on the C3 step than deferring them.
+__device__ __forceinline__ uint32_t row16_cv(int valid, int cnt) { return (uint32_t)cnt | ((uint32_t)valid << 16); }
+template <int NK>
+struct RowStage<NK, true> {
+    static_assert(NK == 1, "16-byte rows: one K");
+    int64_t nrow, s0, cap;
+    double last_t;
+    uint4* R0;    // the kernel's records; the replica's start at record rb (opaque at each
+    int64_t rb;   // store, like the four bases of the array layout)
+    __device__ __forceinline__ void init(double* t, double*, uint32_t*, uint32_t*, int64_t rb_, int64_t cap_)
+    {
+        nrow = 0;
+        s0 = 0;
+        cap = cap_;
+        last_t = -RQ_INF;
+        R0 = reinterpret_cast<uint4*>(t);
+        rb = rb_;
+    }
+    __device__ __forceinline__ void write16(int64_t rr, double t, uint32_t sum, uint32_t cv)
+    {
+        int64_t b = rb;
+        __asm__ volatile("" : "+v"(b));
+        const uint64_t tb = rq_dbl_bits(t);
+        R0[b + rr] = make_uint4((uint32_t)tb, (uint32_t)(tb >> 32), sum, cv);
+    }
+    // row rr of this replica <- (t, sum, valid, cnt); sum is a whole number below 2^32
+    __device__ __forceinline__ void write(int64_t rr, double t, double sum, int valid, const int* cnt)
+    {
+        write16(rr, t, (uint32_t)sum, row16_cv(valid, cnt[0]));
     }
 };
 
@@ -559,8 +599,8 @@ __device__ __forceinline__ bool truncate_tile(int64_t M, int64_t n_events, int& 
 //  nonzero.  Returns true when the row capacity overflowed (stop the replica).
 //  DEFER: the rows go to rs's pending slots (empty on entry: flush_pend() ran since the
 //  last call); rows per replica stay below 2^32 (rows <= 2 x merged entries + 1, int).
-template <int NK, bool DEFER = false>
-__device__ __forceinline__ bool place_rows(RowStage<NK>& rs, uint64_t ma, bool has_o, bool has_w, double ot,
+template <int NK, bool DEFER = false, bool PK = false>
+__device__ __forceinline__ bool place_rows(RowStage<NK, PK>& rs, uint64_t ma, bool has_o, bool has_w, double ot,
                                            double tt, int64_t osum, int oval, const int* ocnt,
                                            int64_t wsum, int wval, const int* wcnt, int& status)
 {
@@ -579,7 +619,12 @@ __device__ __forceinline__ bool place_rows(RowStage<NK>& rs, uint64_t ma, bool h
     const int64_t r0 = rs.nrow - (tie0 ? 1 : 0);
     const int64_t po = r0 + mbcnt64(ko) + mbcnt64(kw);
     const int64_t pw = po + (keep_o ? 1 : 0);
-    if constexpr (DEFER) {
+    if constexpr (PK) {
+        // 16-byte records, stored now: the sums as the integers they are, no conversion
+        static_assert(!DEFER, "16-byte rows are not deferred");
+        if (keep_o && po < rs.cap) rs.write16(po, ot, (uint32_t)osum, row16_cv(oval, ocnt[0]));
+        if (keep_w && pw < rs.cap) rs.write16(pw, tt, (uint32_t)wsum, row16_cv(wval, wcnt[0]));
+    } else if constexpr (DEFER) {
         rs.p_o = keep_o && po < rs.cap ? (uint32_t)po : ~0u;
         rs.p_w = keep_w && pw < rs.cap ? (uint32_t)pw : ~0u;
         rs.p_ot = ot;

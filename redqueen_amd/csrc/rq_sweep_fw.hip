@@ -56,8 +56,12 @@ using namespace rq;
 // two-K instances' too.  The three- and four-K instances stand at 128 VGPRs without the
 // scan and keep a few scratch accesses per tile at any TU, also with the scan as a call
 // (DESIGN §15).
-constexpr int fws_tu(int nk) { return nk == 1 ? 4 : 2; }
-template <int NK>
+// PK (16-byte records, K = 1): a row is four registers until it is used, not six, so the
+// budget of 4 array rows holds 6 records per lane.  4, 6 and 8 all compile to the same spill
+// count and no further scratch access in the tile loop; 6 and 8 measured alike on the C3 step
+// and 4 slightly slower, so 6, the one that fits the old budget.
+constexpr int fws_tu(int nk, bool pk = false) { return nk == 1 ? (pk ? 6 : 4) : 2; }
+template <int NK, bool PK = false>
 __device__ __forceinline__ void fw_scan_rows(int64_t n, double S, double end, const double* Rt, const double* Rs,
                                              const uint32_t* Rv, const uint32_t* Rc, double* lds, double* out)
 {
@@ -74,19 +78,25 @@ __device__ __forceinline__ void fw_scan_rows(int64_t n, double S, double end, co
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     double res[NV];
-    scan_rows<NK, fws_tu(NK), RQ_FWS_NL>(n, S, end, Rt, Rs, Rv, Rc, lds, res);
+    if constexpr (PK)   // Rt: the replica's records
+        scan_rows16<fws_tu(NK, true), RQ_FWS_NL>(n, S, end, reinterpret_cast<const uint4*>(Rt), lds, res);
+    else
+        scan_rows<NK, fws_tu(NK), RQ_FWS_NL>(n, S, end, Rt, Rs, Rv, Rc, lds, res);
     if (lane == 0) {
 #pragma unroll
         for (int s = 0; s < NV; ++s) out[s] = res[s];
     }
 }
+// PK (SCAN, K = 1): the replica's rows as 16-byte records at rows_t (RowStage<1, true>), which
+// only this wave reads; the planner admits it where every field fits (Plan.rows16).
 template <int NK, class COL, int W, int H, bool BITS, bool PW, bool MRG, bool PAIR = false, bool SCAN = false,
-          bool BLK = false>
+          bool BLK = false, bool PK = false>
 __device__ __forceinline__ void sweep_fw_body(SweepArgs a)
 {
     static_assert((W & (W - 1)) == 0 && H <= W, "ring");
     static_assert(!SCAN || MRG, "the sweep's own scan: merged instances only");
     static_assert(!BLK || (MRG && BITS), "event-blocked phase C: the merged sink-bit instances only");
+    static_assert(!PK || (SCAN && NK == 1), "16-byte rows: the sweep's own rows at one K");
     extern __shared__ double lds_g[];
     char* base = reinterpret_cast<char*>(lds_g);
     const int lane = lane_id();
@@ -155,7 +165,8 @@ __device__ __forceinline__ void sweep_fw_body(SweepArgs a)
     do {          \
     } while (0)
 #endif
-    constexpr bool DEFER = MRG && RQ_MRG_DEFER;   // rows stored one tile late (RowStage::flush_pend)
+    // rows stored one tile late (RowStage::flush_pend); 16-byte rows at the end of their own tile
+    constexpr bool DEFER = MRG && RQ_MRG_DEFER && !PK;
     SrcGen gen;
     if (lane < a.n_str && !MRG) gen.init(a.gen, lane, i, etab);
     else gen.none();
@@ -198,7 +209,7 @@ __device__ __forceinline__ void sweep_fw_body(SweepArgs a)
         // agb.F = 0 past nw; BLK: the pad words of the four column blocks too
         if (lane < (BLK ? 4 * RQ_BLK_CB(a.nw) : (a.nw + 1) & ~1)) ft[lane] = make_uint2(agb.F, 0u);
     }
-    RowStage<NK> rs;
+    RowStage<NK, PK> rs;
     const int64_t rbase = rl * a.cap_rows;
     rs.init(a.rows_t, a.rows_sum, a.rows_valid, a.rows_cnt, rbase, a.cap_rows);
 
@@ -567,7 +578,7 @@ __device__ __forceinline__ void sweep_fw_body(SweepArgs a)
         n_events += n + __popcll(ownm);
         posts += __popcll(mo) + __popcll(__ballot(has_w && strm_own));
         world += __popcll(__ballot(has_w && !strm_own));
-        if (ma && place_rows<NK, DEFER>(rs, ma, has_o, has_w, ot, tt, osum, oval, ocnt, wsum, wval, wcnt, status))
+        if (ma && place_rows<NK, DEFER, PK>(rs, ma, has_o, has_w, ot, tt, osum, oval, ocnt, wsum, wval, wcnt, status))
             stop = true;
         RQ_CLK(5);   // rows
         if (stop || fin) break;
@@ -631,10 +642,10 @@ __device__ __forceinline__ void sweep_fw_body(SweepArgs a)
         if (rs.nrow == 0) status |= RQ_ST_EMPTY;
         if (status) atomicOr(&a.status[o], status);
     }
-    if constexpr (SCAN)
-        fw_scan_rows<NK>(rs.nrow, (double)ag.nvalid, a.end, a.rows_t + rbase, a.rows_sum + rbase,
-                         a.rows_valid + rbase, a.rows_cnt + rbase * NK, reinterpret_cast<double*>(wb),
-                         a.metrics + o * (NK + 2));
+    if constexpr (SCAN)   // PK: a record is two doubles of rows_t
+        fw_scan_rows<NK, PK>(rs.nrow, (double)ag.nvalid, a.end, a.rows_t + (PK ? 2 : 1) * rbase, a.rows_sum + rbase,
+                             a.rows_valid + rbase, a.rows_cnt + rbase * NK, reinterpret_cast<double*>(wb),
+                             a.metrics + o * (NK + 2));
     if (!a.wq) break;
     int nx = 0;
     if (lane == 0) nx = atomicAdd(a.wq, 1);
@@ -652,10 +663,10 @@ __global__ __launch_bounds__(1024) void rq_sweep_fw(SweepArgs a)
 #ifndef RQ_FWM_WPE
 #define RQ_FWM_WPE 4
 #endif
-template <int NK, class COL, bool BITS, bool PAIR = false, bool SCAN = false, bool BLK = false>
+template <int NK, class COL, bool BITS, bool PAIR = false, bool SCAN = false, bool BLK = false, bool PK = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(RQ_FWM_WPE))) void rq_sweep_fwm(SweepArgs a)
 {
-    sweep_fw_body<NK, COL, 16, 8, BITS, false, true, PAIR, SCAN, BLK>(a);
+    sweep_fw_body<NK, COL, 16, 8, BITS, false, true, PAIR, SCAN, BLK, PK>(a);
 }
 
 // ============================================================================
@@ -685,11 +696,23 @@ static SweepKernel fwm_nk(int nK)
     }
 }
 // the merged instances: (call pairs) x (the sweep's own scan); the sink-bit ones x (phase C
-// event-blocked)
+// event-blocked); the scanning K = 1 ones x (16-byte rows)
 template <bool PAIR, bool SCAN>
 static SweepKernel fwm_kernel(const SweepInst& i)
 {
     if (i.blk && !i.bits) return nullptr;
+    if (i.pk) {
+        if constexpr (SCAN) {
+            if (i.nK != 1) return nullptr;
+            if (i.bits)
+                return i.blk ? rq_sweep_fwm<1, uint16_t, true, PAIR, true, true, true>
+                             : rq_sweep_fwm<1, uint16_t, true, PAIR, true, false, true>;
+            // int columns mean more than 65535 sinks, which the record's 16-bit fields exclude
+            return i.col16 ? rq_sweep_fwm<1, uint16_t, false, PAIR, true, false, true> : nullptr;
+        } else {
+            return nullptr;
+        }
+    }
     if (i.bits)
         return i.blk ? rq_sweep_fwm<1, uint16_t, true, PAIR, SCAN, true> : rq_sweep_fwm<1, uint16_t, true, PAIR, SCAN>;
     return i.col16 ? fwm_nk<uint16_t, PAIR, SCAN>(i.nK) : fwm_nk<int, PAIR, SCAN>(i.nK);
@@ -703,8 +726,8 @@ static SweepKernel fw_kernel(const SweepInst& i)
             return i.scan ? fwm_kernel<true, true>(i) : fwm_kernel<true, false>(i);
         return i.scan ? fwm_kernel<false, true>(i) : fwm_kernel<false, false>(i);
     }
-    // call pairs, the sweep's own scan, event-blocked phase C: the merged instances only
-    if (i.pair || i.scan || i.blk) return nullptr;
+    // call pairs, the sweep's own scan, event-blocked phase C, 16-byte rows: the merged instances only
+    if (i.pair || i.scan || i.blk || i.pk) return nullptr;
     // OptPWSignificance (PW) instances exist for uint16 columns and W = 16 only (make_plan
     // keeps other PW runs off this path)
     if (i.pw) {
@@ -736,7 +759,7 @@ static hipError_t launch_fw_t(SweepKernel k, const SweepArgs& a, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t rq_launch_sweep_fw(const SweepArgs& a, const SweepInst& i, hipStream_t s)
+hipError_t rq_launch_sweep_fw(const SweepArgs& a, const SweepInst& i, hipStream_t s, size_t rows16_bytes)
 {
     if (a.n_chunk <= 0) return hipSuccess;
     if (i.pair && a.ctrl_kind != RQ_SRC_OPT) return hipErrorInvalidValue;
@@ -745,6 +768,13 @@ hipError_t rq_launch_sweep_fw(const SweepArgs& a, const SweepInst& i, hipStream_
         return hipErrorInvalidValue;
     // event-blocked phase C: the planner's row stride (8-byte reads of a block's words)
     if (i.blk && a.mstride != RQ_BLK_MSTRIDE(a.nw)) return hipErrorInvalidValue;
+    // 16-byte rows: the records of the launch's replicas, 16 * n_chunk * cap_rows bytes from a
+    // 16-byte-aligned rows_t, inside the rows16_bytes the caller has there, and fields that
+    // hold every value (rqh::rows16_fits)
+    if (i.pk && (!a.rows_t || ((uintptr_t)a.rows_t & 15) != 0 ||
+                 (uint64_t)rows16_bytes < (uint64_t)16 * (uint64_t)a.n_chunk * (uint64_t)a.cap_rows ||
+                 !rqh::rows16_fits(i.nK, a.n_sinks, a.mrg_stride)))
+        return hipErrorInvalidValue;
     const SweepKernel k = fw_kernel(i);
     return k ? launch_fw_t(k, a, s) : hipErrorInvalidValue;
 }

@@ -345,11 +345,11 @@ class Graph:
         lib = L.lib()
         if plan_only:
             b.ws_budget = self._ws_budget(dev)
-            info = (C.c_int64 * 10)()
-            L.check("rq_plan_info_n", lib.rq_plan_info_n(self._h, C.byref(b), info, 10))
+            info = (C.c_int64 * 11)()
+            L.check("rq_plan_info_n", lib.rq_plan_info_n(self._h, C.byref(b), info, 11))
             keys = ("variant", "sources_per_lane", "ring_depth", "waves_per_block",
                     "blocks_per_cu", "columns_in_lds", "lds_bytes_per_block", "chunk", "sweep_scan",
-                    "sweep_blk")
+                    "sweep_blk", "sweep_rows16")
             return dict(zip(keys, (int(v) for v in info)))
         return self._run_loop(lib, b, keep, dev, R, Ks, n_grid, n_rep, ck, event_log,
                               gids, check, stream)
